@@ -6,7 +6,18 @@ frame 0) from HBM-resident input to a complete in-memory .lfm: GPU selection
 (8 candidates, 2D entropy) + fused predictor/symbolize kernel over all 64 frames
 + GPU bzip2 of the 3 872 96x96x8 blocks (byte-identical to libbzip2) + D2H of
 the compressed blocks into the pinned .lfm buffer, in order.  Nothing is cached
-between steps.  After the timed steps (N=1) the last .lfm is decoded once
+between steps.
+
+A plain run (`bench.py --gpus N --steps K --warmup W`) sets up, warms up, times
+the K steps and prints the JSON line: `value`, `ms_per_step`, the stage times
+and the predictor's in-pipeline roofline, all taken from the timed steps
+themselves.  `--dump-outputs DIR` also writes what the last timed step handed
+its caller -- the .lfm -- as float32 / float64 .npy files (dump_outputs below);
+the inputs are seeded, so two builds can be compared file for file.  Every
+other leg described below runs only with `--full` (the --no-* options then
+switch single legs off).
+
+With --full, after the timed steps (N=1) the last .lfm is decoded
 (GPU bzip2 decode + GPU inverse predictor) and compared with the input: `decode`
 in the JSON line, for information (not the metric).
 
@@ -21,7 +32,7 @@ compressed blocks and offset-table entries there concurrently
 (lfm.place_slab; equal to lfm.merge_slabs).  Scaling "weak"; a barrier +
 MAX-over-ranks of the timed region gives value.
 
-After the timed steps the last .lfm is checked against the oracle's digests
+With --full the last timed .lfm is checked against the oracle's digests
 (tests/golden/full_size_manifest.json, reference bzip2-1.0.6): the whole-file
 SHA-256 of config 3 at N = 1, per-layer digests of the 512-frame stack at
 N > 1 (`verified` in the JSON line).  At N = 1 the same stack is also encoded
@@ -38,7 +49,8 @@ config-5 round trip; `inproc` -- the drop-in multi-GPU writer
 on config 4 from host memory, on this device and on every visible device.
 
 Also reported: `roofline` of the dominant kernel (fused predictor, HIP-event
-time per launch on its own stream) and `cpu_baseline` = the reference's CPU
+time per launch inside the timed steps; with --full also alone on the GPU and
+`standalone` on its own stream) and, with --full, `cpu_baseline` = the reference's CPU
 bzip2-only path (request 8, same blocks, the reference's own bzip2-1.0.6 from
 oracle/_ref) on a bounded sample, timed on this host.
 """
@@ -170,6 +182,43 @@ def verify_lfm(buf, world, zf):
         ok = ok and hashlib.sha256(buf).hexdigest() == e["sha256"]
     return {"against": "%d layer SHA-256s of the %d-frame stack (oracle, reference bzip2-1.0.6)"
                        % (nlay, len(e["layer_sha256"]) * 8), "ok": bool(ok)}
+
+
+DUMP_SAMPLE = 8 << 20  # .lfm bytes dumped (as float32: 32 MiB); a larger file is sampled
+
+
+def dump_outputs(outdir, buf, nblocks, chosen):
+    """--dump-outputs: the .lfm the last timed step returned to its caller, as
+    .npy files of float32 / float64 (every byte value and every offset below
+    2^53 is exact in them):
+      lfm_nbytes         [1]   f64  the file's length
+      lfm_header         [320] f32  its header bytes
+      lfm_block_ends     [nb]  f64  the u64 offset table (end of every block's stream)
+      lfm_sha256         [32]  f32  SHA-256 of the whole file, so that any byte that
+                                    differs anywhere shows in a comparison
+      lfm_bytes          [n]   f32  the whole file when it has at most DUMP_SAMPLE
+                                    bytes, else the bytes at DUMP_SAMPLE sorted
+                                    positions drawn once from a generator seeded
+                                    with SEED (the same positions for files of
+                                    the same length)
+      chosen_predictor   [1]   f64  the header version the selection settled on"""
+    os.makedirs(outdir, exist_ok=True)
+    a = np.frombuffer(buf, dtype=np.uint8)
+    n = a.size
+    if n > DUMP_SAMPLE:
+        sample = a[np.sort(np.random.default_rng(SEED).integers(0, n, DUMP_SAMPLE))]
+    else:
+        sample = a
+    files = {
+        "lfm_nbytes": np.array([n], dtype=np.float64),
+        "lfm_header": a[:320].astype(np.float32),
+        "lfm_block_ends": np.frombuffer(buf, dtype="<u8", count=nblocks, offset=320).astype(np.float64),
+        "lfm_sha256": np.frombuffer(hashlib.sha256(buf).digest(), dtype=np.uint8).astype(np.float32),
+        "lfm_bytes": sample.astype(np.float32),
+        "chosen_predictor": np.array([chosen], dtype=np.float64),
+    }
+    for name, arr in files.items():
+        np.save(os.path.join(outdir, name + ".npy"), arr)
 
 
 def _free_bytes(d):
@@ -633,6 +682,12 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run every other leg: oracle digest check, unpipelined "
+                         "latency, standalone roofline, host input, decode, configs 1/2/5, inproc, CPU baseline "
+                         "(the --no-* options and --config5-host-volumes apply to these)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the last timed step's .lfm as DIR/<name>.npy (see dump_outputs)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--frames", type=int, default=Z)
     ap.add_argument("--no-decode", action="store_true")
@@ -645,6 +700,8 @@ def main():
     ap.add_argument("--only-config5-host", action="store_true",
                     help="skip the timed encode and every other leg (a long config5_host run)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     # device_count() creates no HIP context on this image: safe before the spawn
     lay = rank_layout(args.gpus, os.environ, torch.cuda.device_count())
@@ -742,10 +799,15 @@ def main():
     if world > 1:
         dist.barrier()
     elapsed = max_over_ranks(time.perf_counter() - t0)
-    # one unpipelined encode (select + encode + every copy, nothing in flight), for its latency
-    t1 = time.perf_counter()
-    _, lat_st = enc.wait(enc.submit(d_img, z0, header_version=0, nnum=T, select_frame=sel_frame), copy=False)
-    latency_ms = max_over_ranks(time.perf_counter() - t1) * 1e3
+    if args.dump_outputs and rank == 0:
+        nb_all = world * ((X + 95) // 96) * ((Y + 95) // 96) * ((zf + 7) // 8)
+        dump_outputs(args.dump_outputs, b if shm is None else shm.buf[:shm.len], nb_all, stats[-1]["chosen"])
+    lat_st = None
+    if args.full:
+        # one unpipelined encode (select + encode + every copy, nothing in flight), for its latency
+        t1 = time.perf_counter()
+        _, lat_st = enc.wait(enc.submit(d_img, z0, header_version=0, nnum=T, select_frame=sel_frame), copy=False)
+        latency_ms = max_over_ranks(time.perf_counter() - t1) * 1e3
 
     px_rank = X * Y * zf
     value = world * px_rank * args.steps / elapsed / 1e6
@@ -790,21 +852,21 @@ def main():
                                "per lane, %d frames per launch)" % zf,
                      "traffic_file": os.path.relpath(tpath, REPO) if traffic is not None else None,
                      "kernel_ms": round(pred_ms, 4), "algorithmic_bytes": alg_bytes,
-                     "read_only_frac": round(px_rank * 2 / (pred_ms / 1e3) / 1e9 / PEAK_HBM_GBS, 4),
-                     # the timed region's launches share the CUs with the previous
-                     # encode's bzip2 tail (the next predictor stage starts before
-                     # that encode is released); the unpipelined latency encode's
-                     # launch has the GPU to itself
-                     "kernel_ms_alone": round(float(lat_st["predict_ms"]), 4),
-                     "frac_alone": round(alg_bytes / (float(lat_st["predict_ms"]) / 1e3) / 1e9 / PEAK_HBM_GBS, 4)},
+                     "read_only_frac": round(px_rank * 2 / (pred_ms / 1e3) / 1e9 / PEAK_HBM_GBS, 4)},
         "stages_ms": {k: round(float(np.mean([s[k] for s in stats])), 3)
                       for k in ("select_ms", "predict_ms", "d2h_ms", "compress_ms", "total_ms")},
         "pipelined": "two encodes in flight (lfm_encoder_submit / wait): an encode's kernels overlap the previous "
                      ".lfm's last payload copies; every .lfm is complete inside the timed region",
-        "latency_ms_per_encode": round(latency_ms, 3),
         "chosen_predictor": stats[-1]["chosen"],
         "ratio": round(px_rank * 2 / out_len, 4),
     }
+    if lat_st is not None:
+        line["latency_ms_per_encode"] = round(latency_ms, 3)
+        # the timed region's launches share the CUs with the previous encode's
+        # bzip2 tail (the next predictor stage starts before that encode is
+        # released); the unpipelined latency encode's launch has the GPU to itself
+        line["roofline"]["kernel_ms_alone"] = round(float(lat_st["predict_ms"]), 4)
+        line["roofline"]["frac_alone"] = round(alg_bytes / (float(lat_st["predict_ms"]) / 1e3) / 1e9 / PEAK_HBM_GBS, 4)
     if place_ms:
         line["stages_ms"]["place_ms"] = round(float(np.mean(place_ms[-args.steps:])), 3)
     # GPU bzip2 stages (HIP events per HIP stream, max over the two streams that
@@ -814,16 +876,16 @@ def main():
         ms = float(np.mean([s["bz_stage_ms"][name] for s in stats]))
         line["stages_ms"]["bz_%s_ms" % name] = round(ms, 3)
         line["stages_ms"]["bz_%s_GBps" % name] = round(bz_in / (ms / 1e3) / 1e9, 1) if ms > 0 else None
+    if rank == 0 and world > 1:
+        line["ratio"] = round(world * px_rank * 2 / shm.len, 4)
     # byte check of the last timed .lfm against the oracle (outside the timed region)
-    if rank == 0:
+    if rank == 0 and args.full:
         buf = b if shm is None else shm.buf[:shm.len]
         line["verified"] = verify_lfm(buf, world, zf)
-        if world > 1:
-            line["ratio"] = round(world * px_rank * 2 / shm.len, 4)
     if world > 1:
         dist.barrier()
         shm.close()
-        if not args.no_inproc:
+        if args.full and not args.no_inproc:
             # the drop-in writer over all N devices, driven from rank 0 alone
             # (what a writeKLBstack / MEX caller on this node gets): every rank
             # first releases its encoder and device memory
@@ -839,10 +901,11 @@ def main():
                 line["inproc"] = inproc_leg(local, node_threads if backend == "nccl" else threads,
                                             [[local], devs])
             dist.barrier(group=cpu_group)
-    if rank == 0 and world == 1:
+    full1 = args.full and rank == 0 and world == 1  # the one-GPU legs that follow
+    if full1:
         line["roofline"]["standalone"] = predictor_standalone(d_img, zf, int(stats[-1]["chosen"]) & 0x7F, alg_bytes)
-    buf = bytes(b) if rank == 0 and world == 1 and not args.no_decode else None  # before b's buffer is reused
-    if rank == 0 and world == 1 and not args.no_host_input:
+    buf = bytes(b) if full1 and not args.no_decode else None  # before b's buffer is reused
+    if full1 and not args.no_host_input:
         line["host_input"] = host_input_rates(enc, d_img, zf)
     if buf is not None:
         # the decode is a reader's job: it runs after the encoder (its buffers,
@@ -867,19 +930,19 @@ def main():
                           "first_ms": round(dlist[0], 1), "runs_ms": [round(x, 1) for x in dlist],
                           "exact": exact,
                           "path": "GPU bzip2 decode + GPU inverse predictor (host libbz2 only for flagged streams, %d threads)" % threads}
-    if rank == 0 and world == 1 and not args.no_small:
+    if full1 and not args.no_small:
         line["configs_1_2"] = small_configs_leg(local, threads)
-    if rank == 0 and world == 1 and not args.no_config5:
+    if full1 and not args.no_config5:
         line["config5"] = config5_leg(local, threads)
-    if rank == 0 and world == 1 and args.config5_host_volumes > 0:
+    if full1 and args.config5_host_volumes > 0:
         line["config5_host"] = config5_host_leg(local, threads, args.config5_host_volumes)
-    if rank == 0 and world == 1 and not args.no_inproc:
+    if full1 and not args.no_inproc:
         nvis = torch.cuda.device_count()
         legs = [[local]] + ([list(range(nvis))] if nvis > 1 else [])
         if os.environ.get("LFM_BENCH_INPROC"):  # e.g. "0,0,0,0": four workers on one GPU (rehearsal)
             legs = [[local], [int(x) for x in os.environ["LFM_BENCH_INPROC"].split(",")]]
         line["inproc"] = inproc_leg(local, threads, legs)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if full1 and not args.no_cpu_baseline:
         line["cpu_baseline"] = cpu_baseline(threads=threads)
         line["cpu_baseline"]["affinity_cpus"] = len(os.sched_getaffinity(0))
         line["cpu_baseline"]["threads_note"] = (

@@ -11,7 +11,7 @@ for r in $(seq 1 $rounds); do
       env:*) envs="${arm#env:}" ;;
       *) envs="" ;;
     esac
-    line=$(env $envs timeout -k 10 240 python3 bench.py $flags 2>>${out%.jsonl}.err | grep '^{') || exit 1
+    line=$(env $envs timeout -k 10 240 python3 bench.py --full $flags 2>>${out%.jsonl}.err | grep '^{') || exit 1
     echo "{\"arm\": \"$arm\", \"round\": $r, \"bench\": $line}" >> $out
     echo "$arm $r done"
   done

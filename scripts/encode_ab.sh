@@ -7,7 +7,7 @@ OUT=$1; shift
 : > "$OUT"
 for rep in 1 2; do
   for e in "$@"; do
-    line=$(env $e timeout -k 10 240 python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-decode \
+    line=$(env $e timeout -k 10 240 python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-decode \
            --no-host-input --no-config5 --no-small --no-inproc --config5-host-volumes 0 2>/dev/null | tail -1)
     rc=$?
     echo "{\"env\": \"$e\", \"rep\": $rep, \"rc\": $rc, \"line\": ${line:-null}}" >> "$OUT"

@@ -13,6 +13,20 @@ REFERENCE = "/root/reference"
 GOLDEN = os.path.join(REPO, "tests", "golden")
 
 
+def golden_predictor_vectors():
+    """The predictor vectors of tests/golden/make_golden.py as one dict, in the
+    order they were written (the arrays are stored in several .npz parts)."""
+    import numpy as np
+    d = os.path.join(GOLDEN, "predictor_vectors")
+    out = {}
+    for name in sorted(os.listdir(d)):
+        if name.endswith(".npz"):
+            with np.load(os.path.join(d, name)) as z:
+                for key in z.files:
+                    out[key] = z[key]
+    return out
+
+
 def pytest_configure(config):
     config.addinivalue_line("markers", "gpu: needs a gfx950 GPU (run with -m gpu)")
     config.addinivalue_line("markers", "slow: long-running")

@@ -4,7 +4,7 @@ Run from the repo root after `make -C oracle`:
     python tests/golden/make_golden.py [--reference /root/reference]
 
 Outputs (all small):
-  predictor_vectors.npz  inputs + expected symbols for every family x predictor
+  predictor_vectors/     inputs + expected symbols for every family x predictor
                          x {spatial, temporal} on edge shapes (W, H not multiples
                          of Nnum, Nnum in {1,2,5,13,15,31,40}, tiny frames, full-range
                          uint16 noise that exercises the int16 wrap)
@@ -54,7 +54,18 @@ def predictor_vectors():
             for k in range(1, 8):
                 out["%s_%s_k%d_z0" % (tag, fam, k)] = O.predict_frame(fr[1], None, T, fam, k, 0)
                 out["%s_%s_k%d_z1" % (tag, fam, k)] = O.predict_frame(fr[1], fr[0], T, fam, k, 1)
-    np.savez_compressed(os.path.join(HERE, "predictor_vectors.npz"), **out)
+    # several parts, each well under 1 MiB (tests/conftest.py golden_predictor_vectors reads them back)
+    d = os.path.join(HERE, "predictor_vectors")
+    os.makedirs(d, exist_ok=True)
+    parts, size = [{}], 0
+    for key, arr in out.items():
+        if parts[-1] and size + arr.nbytes + 256 > 900 * 1024:
+            parts.append({})
+            size = 0
+        parts[-1][key] = arr
+        size += arr.nbytes + 256
+    for i, part in enumerate(parts):
+        np.savez_compressed(os.path.join(d, "part%02d.npz" % i), **part)
     return len(out)
 
 

@@ -9,7 +9,7 @@ import os
 import numpy as np
 import pytest
 
-from conftest import GOLDEN
+from conftest import GOLDEN, golden_predictor_vectors
 
 pytestmark = pytest.mark.gpu
 FAMS = ["tiles", "angle", "space"]
@@ -45,9 +45,9 @@ def run_predict(lfmlib, torch, frames, T, fam, k, video, z0=0, prev=None):
 
 def test_golden_predictor_vectors(lfmlib, gpu):
     torch = gpu
-    g = np.load(os.path.join(GOLDEN, "predictor_vectors.npz"))
+    g = golden_predictor_vectors()
     n = 0
-    for key in g.files:
+    for key in g:
         if not key.startswith("in_"):
             continue
         tag = key[3:]

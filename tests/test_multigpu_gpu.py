@@ -116,7 +116,7 @@ def test_bench_two_ranks_one_shared_lfm(gpu, tmp_path):
     env = dict(os.environ, LFM_BENCH_BACKEND="gloo", OMP_NUM_THREADS="4", LFM_BZ2_GPU_BUDGET_MB="8192")
     env.pop("WORLD_SIZE", None)
     cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--frames", "16", "--steps", "2",
-           "--warmup", "1", "--no-decode", "--no-cpu-baseline"]
+           "--warmup", "1", "--full", "--no-decode", "--no-cpu-baseline"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=400, env=env, cwd=str(tmp_path))
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
@@ -138,7 +138,7 @@ def test_bench_inproc_leg_four_workers(gpu, tmp_path):
     from conftest import REPO
     env = dict(os.environ, LFM_BENCH_INPROC="0,0,0,0", LFM_BZ2_GPU_BUDGET_MB="8192")
     cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--steps", "1", "--warmup", "1", "--frames", "16",
-           "--no-decode", "--no-cpu-baseline", "--no-host-input", "--no-config5"]
+           "--full", "--no-decode", "--no-cpu-baseline", "--no-host-input", "--no-config5"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=300, env=env, cwd=str(tmp_path))
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])

@@ -7,7 +7,7 @@ import struct
 import numpy as np
 import pytest
 
-from conftest import GOLDEN, REFERENCE, REPO
+from conftest import GOLDEN, REFERENCE, REPO, golden_predictor_vectors
 
 KAT = os.path.join(GOLDEN, "bzip2_kat")
 
@@ -123,9 +123,9 @@ def test_symbolize_bijective(oracle):
 
 
 def test_golden_predictor_vectors(oracle):
-    g = np.load(os.path.join(GOLDEN, "predictor_vectors.npz"))
+    g = golden_predictor_vectors()
     n = 0
-    for key in g.files:
+    for key in g:
         if not key.startswith("in_"):
             continue
         tag = key[3:]
