@@ -812,14 +812,22 @@ __global__ __launch_bounds__(NT) void bzd_walk(Dec D)
         mres[id] = res;
     }
     __syncthreads();
-    // chain the segments from the start (one lane)
+    // chain the segments from the start (one lane).  The markers of the
+    // start's cycle follow each other in a ring, so the chain is back at its
+    // first segment after one trip round that cycle: if that comes before
+    // every segment has had its turn there are several cycles (a periodic
+    // text), and further trips must not count (w w with two walkers, one per
+    // cycle, would reach off == n and k == nwalk on the second trip, leaving
+    // the other segment's mstart unwritten)
     if (t == 0) {
-        uint32_t id = extra ? nm : v0 / kMark, off = 0, k = 0;
+        const uint32_t id0 = extra ? nm : v0 / kMark;
+        uint32_t id = id0, off = 0, k = 0;
         while (k < nwalk && off < n) {
             mstart[id] = off;
             off += mlen[id];
             id = mnext[id];
             ++k;
+            if (id == id0) break;
         }
         s_total = off == n && k == nwalk ? 1u : 0u;
     }
