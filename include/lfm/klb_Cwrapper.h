@@ -46,7 +46,9 @@ DECLSPECIFIER void* readKLBstack(const char* filename, uint32_t xyzct[KLB_DATA_D
 
 DECLSPECIFIER int readKLBstackInPlace(const char* filename, void* im, enum KLB_DATA_TYPE* dataType, int numThreads);
 
-/* inclusive bounds; decodes the full image and crops (correct with predictors) */
+/* inclusive bounds; decodes only the blocks the region depends on (with a
+ * predictor: the frames' blocks up and left of it, and the frame before an odd
+ * z of a video stack) and crops, so it is correct with predictors */
 DECLSPECIFIER int readKLBroiInPlace(const char* filename, void* im, uint32_t xyzctLB[KLB_DATA_DIMS],
                                     uint32_t xyzctUB[KLB_DATA_DIMS], int numThreads);
 

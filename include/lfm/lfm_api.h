@@ -182,6 +182,44 @@ LFM_API int lfm_decode_memory(const uint8_t* buf, uint64_t len, void* img, int n
 LFM_API int lfm_decode_memory_roi(const uint8_t* buf, uint64_t len, const uint32_t lb[KLB_DATA_DIMS],
                                   const uint32_t ub[KLB_DATA_DIMS], void* out, uint64_t out_bytes, int numThreads);
 
+/* What a device-destination decode did (the two functions below). */
+typedef struct lfm_decode_stats {
+    double   total_ms;
+    int      path;         /* 0: pipelined GPU decode wrote the caller's buffer; 1: host decode + upload */
+    uint32_t chunks;       /* pipeline chunks (0 on path 1) */
+    uint64_t blocks;       /* streams decoded */
+    uint64_t host_blocks;  /* of them handed to the host library (all of them on path 1) */
+    uint64_t d2h_bytes;    /* image bytes copied device -> host during the call */
+    uint64_t staged_bytes; /* device sub-image the region read decoded before cropping (0: exact / whole) */
+} lfm_decode_stats;
+
+/* lfm_decode_memory / lfm_decode_memory_roi into DEVICE memory: d_img / d_out
+ * is a device pointer (hipMalloc, a torch CUDA tensor's data_ptr) of at least
+ * the image's / region's bytes in the file's data type, x fastest.  The
+ * decode runs on the buffer's device (found with hipPointerGetAttributes; the
+ * caller's current device is restored) and no image byte goes through host
+ * memory: the inverse predictor, or for unpredicted files the block scatter,
+ * writes the buffer, and a region that is not exactly a box of blocks is
+ * cropped on the device from a sub-image the library keeps there.
+ * Ordering: the library's first write to the buffer comes after all work
+ * queued on the device's null stream when the call is made (a producer on
+ * another stream must be synchronised by the caller); when the call returns
+ * 0, all library work on the buffer is complete and host-synchronised, so any
+ * stream may read it.  When it returns non-zero the buffer's contents are
+ * unspecified.
+ * Files the pipelined GPU decode does not take (compression NONE / ZLIB,
+ * Nnum > 31, non-contiguous block offsets, LFM_GPU_DECODE=0 or
+ * LFM_GPU_BUNZIP2=0, device memory exhausted) are decoded on the host as
+ * lfm_decode_memory does into a temporary and uploaded with one copy:
+ * stats->path = 1.
+ * Return codes as the host functions', and 3 for a host or unregistered
+ * pointer or a buffer smaller than the image / region.  stats may be NULL. */
+LFM_API int lfm_decode_memory_device(const uint8_t* buf, uint64_t len, void* d_img, uint64_t d_img_bytes,
+                                     int numThreads, lfm_decode_stats* stats);
+LFM_API int lfm_decode_memory_roi_device(const uint8_t* buf, uint64_t len, const uint32_t lb[KLB_DATA_DIMS],
+                                         const uint32_t ub[KLB_DATA_DIMS], void* d_out, uint64_t out_bytes,
+                                         int numThreads, lfm_decode_stats* stats);
+
 #ifdef __cplusplus
 }
 #endif

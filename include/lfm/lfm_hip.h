@@ -133,6 +133,16 @@ int lfm_hip_bunzip2_issue(const void* d_payload, const uint64_t* h_offs, uint32_
 int lfm_hip_scatter_blocks(const void* d_blocks, uint32_t stride, uint32_t first, uint32_t count,
                            const uint32_t dims[5], const uint32_t bs[5], uint32_t bpp, void* d_img, void* stream);
 
+/* The box lb .. lb + n - 1 (xyzct, x fastest) of a device image of src_dims
+ * (bpp = 1, 2, 4 or 8 bytes per sample) into the dense device array d_dst of
+ * n[4] * ... * n[0] samples; d_dst must not overlap the image.  Rows are
+ * copied in 16-byte accesses where a row's two addresses differ by a multiple
+ * of 16 (single bytes up to the first boundary and after the last), else in
+ * 4-, 2- or 1-byte accesses.  EINVAL for a zero extent, a box that leaves the
+ * image or another bpp.  Asynchronous. */
+int lfm_hip_crop_region(const void* d_src, const uint32_t src_dims[5], const uint32_t lb[5], const uint32_t n[5],
+                        uint32_t bpp, void* d_dst, void* stream);
+
 /* Synthetic light-field stack of SURVEY.md 8(d) (integer generator) written
  * straight into device memory: frames z0 .. z0+Z-1 (X*Y pixels each) of
  * volume (c, t) = (0, t_index), global pixel index offset idx0 (a z-slab of a

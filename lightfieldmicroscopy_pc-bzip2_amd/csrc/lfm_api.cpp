@@ -253,6 +253,23 @@ extern "C" int lfm_decode_memory(const uint8_t* buf, uint64_t len, void* img, in
     return rc;
 }
 
+extern "C" int lfm_decode_memory_device(const uint8_t* buf, uint64_t len, void* d_img, uint64_t d_img_bytes,
+                                        int numThreads, lfm_decode_stats* stats)
+{
+    const int rc = lfm::decode_memory_device(buf, len, nullptr, nullptr, d_img, d_img_bytes, numThreads, stats);
+    if (std::getenv("LFM_DECODE_TIMING") && stats)
+        std::fprintf(stderr, "decode total (C, device) %8.2f ms\n", stats->total_ms);
+    return rc;
+}
+
+extern "C" int lfm_decode_memory_roi_device(const uint8_t* buf, uint64_t len, const uint32_t lb[KLB_DATA_DIMS],
+                                            const uint32_t ub[KLB_DATA_DIMS], void* d_out, uint64_t out_bytes,
+                                            int numThreads, lfm_decode_stats* stats)
+{
+    if (!lb || !ub) return 3;
+    return lfm::decode_memory_device(buf, len, lb, ub, d_out, out_bytes, numThreads, stats);
+}
+
 extern "C" int lfm_decode_memory_roi(const uint8_t* buf, uint64_t len, const uint32_t lb[KLB_DATA_DIMS],
                                      const uint32_t ub[KLB_DATA_DIMS], void* out, uint64_t out_bytes, int numThreads)
 {

@@ -2096,7 +2096,8 @@ bool staged_d2h(void* h_dst, const void* d_src, size_t n, hipStream_t st, int th
 // chunks of gpu_decode.
 struct DecodeBuffers {
     static constexpr int kSlots = 3;
-    enum { PAY, SYM, OUT, WS0, BLK0 = WS0 + kSlots, N = BLK0 + kSlots };
+    // (ROI: the sub-image a device-destination region read crops from)
+    enum { PAY, SYM, OUT, ROI, WS0, BLK0 = WS0 + kSlots, N = BLK0 + kSlots };
     int dev = -1;
     hipStream_t st[kSlots] = {};
     hipStream_t dl = nullptr;                // the downloads' device -> pinned copies
@@ -2111,9 +2112,13 @@ struct DecodeBuffers {
     DecodeBuffers(const DecodeBuffers&) = delete;
     DecodeBuffers& operator=(const DecodeBuffers&) = delete;
     ~DecodeBuffers() { release(); }  // a worker thread that exits frees its device buffers
+    // a device-destination region read is between its sub-image's decode and
+    // the crop: release() (LFM_DECODE_KEEP=0, a failed allocation) spares ROI
+    bool hold_roi = false;
     void release()
     {
         for (int i = 0; i < N; ++i) {
+            if (hold_roi && i == ROI) continue;
             if (p[i]) (void)hipFree(p[i]);
             p[i] = nullptr;
             cap[i] = 0;
@@ -2159,12 +2164,16 @@ struct DecodeBuffers {
         }
         return true;
     }
-    void* get(int i, size_t bytes)
+    void drop(int i)
     {
-        if (cap[i] >= bytes) return p[i];
         if (p[i]) (void)hipFree(p[i]);
         p[i] = nullptr;
         cap[i] = 0;
+    }
+    void* get(int i, size_t bytes)
+    {
+        if (cap[i] >= bytes) return p[i];
+        drop(i);
         if (hipMalloc(&p[i], bytes) != hipSuccess) {
             (void)hipGetLastError();
             p[i] = nullptr;
@@ -2206,6 +2215,9 @@ DecodeBuffers& decode_buffers()
     static thread_local DecodeBuffers b;
     return b;
 }
+
+// image bytes this thread's decodes have copied device -> host (lfm_decode_stats.d2h_bytes)
+thread_local uint64_t tl_d2h_bytes = 0;
 } // namespace
 
 void par_memcpy(void* dst, const void* src, size_t n, int threads) { par_memcpy_impl(dst, src, n, threads); }
@@ -2220,14 +2232,22 @@ void par_memcpy(void* dst, const void* src, size_t n, int threads) { par_memcpy_
 // device: while chunk c's kernels run, chunk c - 1 is finished and copied
 // down and chunk c + 1's payload goes up.  Returns -1 when the GPU path does
 // not apply (the caller decodes on the host).
+// With dd, img is device memory on the current device and takes the place of
+// the device image the pixels are finished in (OUT of a predicted file, SYM of
+// an unpredicted one, which is then not allocated): nothing comes down, the
+// downloader thread only waits for each chunk's event and checks its status
+// words, and every slot stream waits for dd->after_caller before the chunk's
+// first kernel that writes img.
 static int gpu_decode(const uint8_t* payload, size_t len, const klb_image_header& h, uint8_t* img, int family,
-                      bool predicted, int k, int video, int threads)
+                      bool predicted, int k, int video, int threads, DeviceDest* dd = nullptr)
 {
     const BlockGrid g(h);
     const uint64_t nb = g.nblocks;
     const size_t bpp = h.getBytesPerPixel();
     const uint32_t block_bytes = h.getBlockSizeBytes();
     if (!nb || !block_bytes || nb >= (1ull << 31)) return -1;
+    // (the scatter's and the inverse predictor's 16-byte rows)
+    if (dd && ((uintptr_t)img & 15)) return -1;
     // LFM_DECODE_TIMING=1: stage times on stderr
     static const bool timing = env_int("LFM_DECODE_TIMING", 0) != 0;
     using clk = std::chrono::steady_clock;
@@ -2281,8 +2301,8 @@ static int gpu_decode(const uint8_t* payload, size_t len, const klb_image_header
     const uint64_t us_per = spc + 1;
     if (DB.begin()) {
         d_pay = DB.get(DecodeBuffers::PAY, offs[nb] + 64);
-        d_sym = DB.get(DecodeBuffers::SYM, img_bytes);
-        d_out = predicted ? DB.get(DecodeBuffers::OUT, img_bytes) : nullptr;
+        d_sym = dd && !predicted ? img : DB.get(DecodeBuffers::SYM, img_bytes);
+        d_out = !predicted ? nullptr : dd ? img : DB.get(DecodeBuffers::OUT, img_bytes);
         for (int q = 0; q < nslot; ++q) {
             d_ws[q] = DB.get(DecodeBuffers::WS0 + q, ws);
             d_blk[q] = DB.get(DecodeBuffers::BLK0 + q, batch * block_bytes);
@@ -2370,7 +2390,7 @@ static int gpu_decode(const uint8_t* payload, size_t len, const klb_image_header
         });
         mark("prefault-started", 0);
     };
-    if (prefault_mode == 1) start_prefault();
+    if (prefault_mode == 1 && !dd) start_prefault();
     // the 64 zero bytes past the payload (the bit window's lookahead of the
     // last stream): LFM_DECODE_SLACK=1 queues them on the last chunk's stream
     // (stream order puts them before its kernels), 0 synchronises here
@@ -2389,6 +2409,7 @@ static int gpu_decode(const uint8_t* payload, size_t len, const klb_image_header
     mark("events", 0);
     // host side of chunk c once its streams are decoded: host-library blocks,
     // then scatter and inverse predictor queued behind them (no wait)
+    uint64_t host_blocks = 0;
     auto finish = [&](uint64_t c) -> int {
         const int q = (int)(c % nslot);
         hipStream_t st = DB.st[q];
@@ -2404,6 +2425,7 @@ static int gpu_decode(const uint8_t* payload, size_t len, const klb_image_header
             g.block(b0 + i, o, sz);
             const uint64_t expect = bpp * sz[0] * sz[1] * sz[2] * sz[3] * sz[4];
             if (flags[i] == 1) {  // the host library decodes this stream
+                ++host_blocks;
                 const int r = decompress_one(BZIP2, payload + offs[b0 + i], (uint32_t)(offs[b0 + i + 1] - offs[b0 + i]),
                                              hb.data(), (uint32_t)expect);
                 if (r) return r;
@@ -2417,12 +2439,16 @@ static int gpu_decode(const uint8_t* payload, size_t len, const klb_image_header
                 return 2;
             }
         }
+        // a device destination is first written by the scatter (unpredicted)
+        // or the inverse predictor: after the caller's null-stream work
+        if (dd && !predicted && hipStreamWaitEvent(st, dd->after_caller, 0) != hipSuccess) return 3;
         if (lfm_hip_scatter_blocks(d_blk[q], block_bytes, (uint32_t)b0, (uint32_t)cnt, dims, bs, (uint32_t)bpp, d_sym,
                                    st) != LFM_HIP_OK)
             return 3;
         if (predicted) {
             uint64_t f0, f1;
             frames(c, f0, f1);
+            if (dd && hipStreamWaitEvent(st, dd->after_caller, 0) != hipSuccess) return 3;
             // a temporal first frame (video, odd z) reads the previous chunk's
             // last decoded frame: wait for that chunk's inverse predictor
             if (video && c > 0 && hipStreamWaitEvent(st, cev[c - 1], 0) != hipSuccess) return 3;
@@ -2455,6 +2481,7 @@ static int gpu_decode(const uint8_t* payload, size_t len, const klb_image_header
     uint64_t dl_ready = 0;  // chunks [0, dl_ready) may be downloaded
     bool dl_stop = false;
     int drc = 0;
+    uint64_t d2h_bytes = 0;  // (the downloader's; read after its join)
     int dev = 0;
     (void)hipGetDevice(&dev);
     std::thread downloader([&]() {
@@ -2490,6 +2517,10 @@ static int gpu_decode(const uint8_t* payload, size_t len, const klb_image_header
                         drc = 3;
                         return;
                     }
+            if (dd) {  // the pixels are where they belong
+                mark("dl-end", c);
+                continue;
+            }
             // the device -> pinned copies: the runtime's (57 GB/s) or an SDMA
             // engine's (28 GB/s).  The runtime's copies slow the kernels of
             // chunks still decoding (config 5, 8 chunks: 403-427 vs 325-349
@@ -2505,6 +2536,7 @@ static int gpu_decode(const uint8_t* payload, size_t len, const klb_image_header
                 return;
             }
             t_down += ms(t0, clk::now());
+            d2h_bytes += n;
             mark("dl-end", c);
         }
     });
@@ -2526,7 +2558,7 @@ static int gpu_decode(const uint8_t* payload, size_t len, const klb_image_header
         }
         t_up += ms(t0, clk::now());
         mark("uploaded", c);
-        if (c == 0 && prefault_mode == 2) start_prefault();
+        if (c == 0 && prefault_mode == 2 && !dd) start_prefault();
         if (lfm_hip_bunzip2_issue(d_pay, offs.data() + b0, (uint32_t)cnt, d_blk[q], block_bytes, d_ws[q], ws, hs[q],
                                   hs[q] + batch, DB.st[q]) != LFM_HIP_OK) {
             rc = 3;
@@ -2548,6 +2580,7 @@ static int gpu_decode(const uint8_t* payload, size_t len, const klb_image_header
     }
     dcv.notify_all();
     downloader.join();
+    tl_d2h_bytes += d2h_bytes;
     mark("joined", nch);
     if (prefault.joinable()) prefault.join();  // (not reached: the downloader joins it first)
     if (!rc) rc = drc;
@@ -2566,12 +2599,17 @@ static int gpu_decode(const uint8_t* payload, size_t len, const klb_image_header
                      "after wait %.2f, download %.2f, total %.2f ms\n",
                      (unsigned long long)nch, (unsigned long long)batch, ms(t_start, t_alloc), t_up, t_wait, t_host,
                      t_down, ms(t_start, clk::now()));
+    if (dd) {
+        dd->stats.chunks = (uint32_t)nch;
+        dd->stats.blocks = nb;
+        dd->stats.host_blocks = host_blocks;
+    }
     release();
     return rc;
 }
 
 int decode_payload(const uint8_t* payload, size_t len, const klb_image_header& h, uint8_t* img, int threads,
-                   int family)
+                   int family, DeviceDest* dd)
 {
     if (threads <= 0) threads = default_threads();
     const BlockGrid g(h);
@@ -2584,6 +2622,31 @@ int decode_payload(const uint8_t* payload, size_t len, const klb_image_header& h
     if (predicted && (k > 7 || h.Nnum == 0)) {
         std::printf("ERROR: unknown predictor %d in header\n", k);
         return 3;
+    }
+    if (dd) {
+        // device destination: the pipelined decode writes img itself, or the
+        // host reader below (this function without dd) fills a temporary that
+        // one copy uploads, on the null stream and so behind the caller's work
+        if (h.compressionType == BZIP2 && gpu_decode_enabled() && gpu_bunzip2_enabled() &&
+            (!predicted || h.Nnum <= 31)) {
+            const int rc = gpu_decode(payload, len, h, img, family, predicted, k, video, threads, dd);
+            if (rc != -1) {
+                dd->stats.path = 0;
+                return rc;
+            }
+        }
+        const size_t n = h.getImageSizeBytes();
+        std::unique_ptr<uint8_t[]> tmp(new uint8_t[n]);  // (no zero fill: every byte is decoded)
+        const uint64_t down0 = tl_d2h_bytes;
+        const int rc = decode_payload(payload, len, h, tmp.get(), threads, family);
+        if (rc) return rc;
+        dd->stats.path = 1;
+        dd->stats.chunks = 0;
+        dd->stats.blocks = dd->stats.host_blocks = g.nblocks;
+        // (the host reader's inverse predictor runs on the GPU when one is
+        // visible: its pixels came down before they go up again here)
+        dd->stats.d2h_bytes += tl_d2h_bytes - down0;
+        return hipMemcpy(img, tmp.get(), n, hipMemcpyHostToDevice) == hipSuccess ? 0 : 3;
     }
     if (h.compressionType == BZIP2 && gpu_decode_enabled() && gpu_bunzip2_enabled() && lfm_hip_device_count() > 0 &&
         (!predicted || h.Nnum <= 31)) {
@@ -2642,6 +2705,7 @@ int decode_payload(const uint8_t* payload, size_t len, const klb_image_header& h
             if (hr != LFM_HIP_OK || hipMemcpyAsync(o16 + v * Z * fs, d_o, vb, hipMemcpyDeviceToHost, st) != hipSuccess ||
                 hipStreamSynchronize(st) != hipSuccess)
                 rc = 3;
+            tl_d2h_bytes += vb;
         }
         if (d_s) (void)hipFree(d_s);
         if (d_o) (void)hipFree(d_o);
@@ -2686,7 +2750,7 @@ int decode_payload(const uint8_t* payload, size_t len, const klb_image_header& h
 // as if they were the whole frame, which is wrong with predictors
 // (klb_imageIO.cpp:2614-2682).
 int decode_roi(const uint8_t* payload, size_t len, const klb_image_header& h, const uint32_t lb[5],
-               const uint32_t ub[5], uint8_t* out, int threads, int family)
+               const uint32_t ub[5], uint8_t* out, int threads, int family, DeviceDest* dd)
 {
     const BlockGrid g(h);
     if (g.nblocks != h.Nb) return 3;
@@ -2751,7 +2815,37 @@ int decode_roi(const uint8_t* payload, size_t len, const klb_image_header& h, co
     // decoded straight into `out`: no temporary image, no crop
     bool exact = true;
     for (int d = 0; d < 5; ++d) exact = exact && o[d] == lb[d] && n[d] == (uint64_t)ub[d] - lb[d] + 1;
-    if (exact) return decode_payload(spay, total, sub, out, threads, family);
+    if (exact) return decode_payload(spay, total, sub, out, threads, family, dd);
+    if (dd) {
+        // the sub-image is decoded into a device buffer kept between calls and
+        // the region copied out of it on the device, behind the caller's work
+        static const bool keep = env_int("LFM_DECODE_KEEP", 1) != 0;
+        DecodeBuffers& DB = decode_buffers();
+        const size_t sbytes = sub.getImageSizeBytes();
+        void* d_sub = DB.begin() ? DB.get(DecodeBuffers::ROI, sbytes) : nullptr;
+        if (!d_sub) return 3;
+        DB.hold_roi = true;
+        dd->stats.staged_bytes = sbytes;
+        int rc = decode_payload(spay, total, sub, (uint8_t*)d_sub, threads, family, dd);
+        if (!rc && !DB.begin()) rc = 3;  // (its streams again, had the decode released them)
+        uint32_t sdims[5], slb[5], sn[5];
+        for (int d = 0; d < 5; ++d) {
+            sdims[d] = (uint32_t)n[d];
+            slb[d] = (uint32_t)(lb[d] - o[d]);
+            sn[d] = ub[d] - lb[d] + 1;
+        }
+        hipStream_t st = DB.st[0];
+        if (!rc && (hipStreamWaitEvent(st, dd->after_caller, 0) != hipSuccess ||
+                    lfm_hip_crop_region(d_sub, sdims, slb, sn, (uint32_t)bpp, out, st) != LFM_HIP_OK ||
+                    hipStreamSynchronize(st) != hipSuccess))
+            rc = 3;
+        DB.hold_roi = false;
+        if (!keep) {
+            DB.release();
+            staging().release();
+        }
+        return rc;
+    }
     std::unique_ptr<uint8_t[]> simg(new uint8_t[sub.getImageSizeBytes()]);  // (no zero fill: every byte is decoded)
     const int rc = decode_payload(spay, total, sub, simg.get(), threads, family);
     if (rc) return rc;
@@ -2766,6 +2860,49 @@ int decode_roi(const uint8_t* payload, size_t len, const klb_image_header& h, co
         std::memcpy(out + r * row, simg.get() + e * bpp, row);
     });
     return 0;
+}
+
+int decode_memory_device(const uint8_t* buf, uint64_t len, const uint32_t* lb, const uint32_t* ub, void* d_out,
+                         uint64_t out_bytes, int threads, lfm_decode_stats* stats)
+{
+    const auto t0 = std::chrono::steady_clock::now();
+    if (!buf || !d_out || (lb == nullptr) != (ub == nullptr)) return 3;
+    klb_image_header h;
+    int rc = h.parseHeader(buf, len);
+    if (rc) return rc;
+    uint64_t need = h.getImageSizeBytes();
+    if (lb) {
+        need = h.getBytesPerPixel();  // the region in the file's own data type
+        for (int d = 0; d < KLB_DATA_DIMS; ++d) {
+            if (ub[d] < lb[d] || ub[d] >= h.xyzct[d]) return 3;
+            need *= (uint64_t)(ub[d] - lb[d] + 1);
+        }
+    }
+    if (!need || out_bytes < need || lfm_hip_device_count() <= 0) return 3;
+    hipPointerAttribute_t attr;
+    if (hipPointerGetAttributes(&attr, d_out) != hipSuccess) {
+        (void)hipGetLastError();  // (a pointer the runtime has never seen)
+        return 3;
+    }
+    if (attr.type != hipMemoryTypeDevice) return 3;
+    int cur = 0;
+    if (hipGetDevice(&cur) != hipSuccess) return 3;
+    if (attr.device != cur && hipSetDevice(attr.device) != hipSuccess) return 3;
+    DeviceDest dd;
+    // what the caller has queued on the buffer's device (its null stream)
+    // comes before the library's first write
+    if (hipEventCreateWithFlags(&dd.after_caller, hipEventDisableTiming) != hipSuccess ||
+        hipEventRecord(dd.after_caller, nullptr) != hipSuccess)
+        rc = 3;
+    const size_t hs = h.getSizeInBytes();
+    if (!rc)
+        rc = lb ? decode_roi(buf + hs, len - hs, h, lb, ub, (uint8_t*)d_out, threads, current_family(), &dd)
+                : decode_payload(buf + hs, len - hs, h, (uint8_t*)d_out, threads, current_family(), &dd);
+    if (dd.after_caller) (void)hipEventDestroy(dd.after_caller);
+    if (attr.device != cur) (void)hipSetDevice(cur);
+    dd.stats.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    if (stats) *stats = dd.stats;
+    return rc;
 }
 
 int decode_file_roi(const char* filename, klb_image_header& h, const uint32_t lb[5], const uint32_t ub[5],

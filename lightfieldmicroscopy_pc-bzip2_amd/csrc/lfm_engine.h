@@ -288,14 +288,40 @@ int encode_multi(const void* img, klb_image_header& h, Sink& sink, lfm_encode_st
 // so the payloads concatenate and the offset table is re-accumulated.
 int merge_slabs(const uint8_t* const* slabs, const uint64_t* lens, int n, std::vector<uint8_t>* out);
 
-// Decode the payload of a .lfm (bytes after the header) into img.
+// A decode whose destination is device memory (lfm_decode_memory_device,
+// lfm_decode_memory_roi_device): `img` / `out` of decode_payload / decode_roi
+// is then a device pointer on the current device.  The pipelined GPU decode
+// writes it directly (the inverse predictor's output, or the block scatter of
+// an unpredicted file): no second device image, no prefault thread, no pinned
+// download staging, no device -> host copy of image bytes.  Every library
+// stream waits for `after_caller` (recorded on the null stream when the call
+// came in) before its first write; on a successful return all library work on
+// the buffer is complete and host-synchronised.  On failure the buffer's
+// contents are unspecified.  Files the pipelined decode does not take are
+// decoded on the host as ever into a temporary and uploaded with one copy
+// (stats.path = 1).
+struct DeviceDest {
+    lfm_decode_stats stats{};
+    hipEvent_t after_caller = nullptr;
+};
+
+// Decode the payload of a .lfm (bytes after the header) into img (host memory,
+// or device memory when dd is given).
 int decode_payload(const uint8_t* payload, size_t len, const klb_image_header& h, uint8_t* img, int threads,
-                   int family);
+                   int family, DeviceDest* dd = nullptr);
 int decode_file(const char* filename, klb_image_header& h, std::vector<uint8_t>* img_out, uint8_t* img_into,
                 int threads);
-// ROI read: only the blocks the ROI depends on are decoded (lb / ub inclusive)
+// ROI read: only the blocks the ROI depends on are decoded (lb / ub inclusive).
+// With dd, `out` is device memory: an exact region decodes straight into it,
+// any other decodes its sub-image into a kept device buffer and
+// lfm_hip_crop_region writes `out` (stats.staged_bytes = that sub-image).
 int decode_roi(const uint8_t* payload, size_t len, const klb_image_header& h, const uint32_t lb[5],
-               const uint32_t ub[5], uint8_t* out, int threads, int family);
+               const uint32_t ub[5], uint8_t* out, int threads, int family, DeviceDest* dd = nullptr);
+// The two device-destination readers behind the C ABI: find the buffer's
+// device (3 for a host or unregistered pointer), run the decode there with the
+// ordering of DeviceDest and restore the caller's current device.
+int decode_memory_device(const uint8_t* buf, uint64_t len, const uint32_t* lb, const uint32_t* ub, void* d_out,
+                         uint64_t out_bytes, int threads, lfm_decode_stats* stats);
 int decode_file_roi(const char* filename, klb_image_header& h, const uint32_t lb[5], const uint32_t ub[5],
                     uint8_t* out, int threads);
 

@@ -37,12 +37,13 @@ EXPORTS = [
     "lfm_encoder_create", "lfm_encoder_destroy", "lfm_encoder_encode", "lfm_encoder_encode_slab",
     "lfm_merge_slabs", "lfm_free", "lfm_decode_memory", "lfm_decode_memory_roi", "lfm_set_devices", "lfm_get_devices", "lfm_default_devices",
     "lfm_encoder_encode_multi", "lfm_release_encoders", "lfm_slab_info", "lfm_place_slab", "lfm_encoder_submit",
-    "lfm_encoder_submit_select", "lfm_encoder_wait",
+    "lfm_encoder_submit_select", "lfm_encoder_wait", "lfm_decode_memory_device", "lfm_decode_memory_roi_device",
     # lfm_hip.h
     "lfm_hip_predict", "lfm_hip_unpredict", "lfm_hip_unpredict_async", "lfm_hip_unpredict_check",
     "lfm_hip_predict_candidates", "lfm_hip_entropy2d", "lfm_hip_select_workspace_bytes", "lfm_hip_select",
     "lfm_hip_synth", "lfm_hip_device_count", "lfm_hip_force_generic", "lfm_hip_bzip2_workspace_bytes",
     "lfm_hip_bzip2_blocks", "lfm_hip_bzip2_last_stage_ms", "lfm_hip_bunzip2_workspace_bytes", "lfm_hip_bunzip2_blocks", "lfm_hip_scatter_blocks",
+    "lfm_hip_crop_region",
 ]
 
 
@@ -62,6 +63,16 @@ class EncodeStats(ctypes.Structure):
         d["entropy"] = list(self.entropy)
         d["bz_stage_ms"] = dict(zip(self.BZ_STAGES, list(self.bz_stage_ms)))
         return d
+
+
+class DecodeStats(ctypes.Structure):
+    """lfm_decode_stats (lfm_api.h)."""
+    _fields_ = [("total_ms", ctypes.c_double), ("path", ctypes.c_int), ("chunks", ctypes.c_uint32),
+                ("blocks", ctypes.c_uint64), ("host_blocks", ctypes.c_uint64), ("d2h_bytes", ctypes.c_uint64),
+                ("staged_bytes", ctypes.c_uint64)]
+
+    def as_dict(self):
+        return {f: getattr(self, f) for f, _ in self._fields_}
 
 
 _lib = None
@@ -153,6 +164,16 @@ def lib():
                                  ctypes.POINTER(ctypes.c_int), vp, vp]
     L.lfm_hip_synth.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                 ctypes.c_int, ctypes.c_uint64, ctypes.c_uint64, vp]
+    # the device-destination readers and the region copy: a library built
+    # before them still loads for everything else
+    if hasattr(L, "lfm_decode_memory_device"):
+        L.lfm_decode_memory_device.argtypes = [vp, ctypes.c_uint64, vp, ctypes.c_uint64, ctypes.c_int,
+                                               ctypes.POINTER(DecodeStats)]
+    if hasattr(L, "lfm_decode_memory_roi_device"):
+        L.lfm_decode_memory_roi_device.argtypes = [vp, ctypes.c_uint64, u32p, u32p, vp, ctypes.c_uint64, ctypes.c_int,
+                                                   ctypes.POINTER(DecodeStats)]
+    if hasattr(L, "lfm_hip_crop_region"):
+        L.lfm_hip_crop_region.argtypes = [vp, u32p, u32p, u32p, ctypes.c_uint32, vp, vp]
     _lib = L
     return L
 
@@ -526,11 +547,126 @@ def decode_roi(buf, lb, ub, dtype=None, num_threads=-1, out=None):
     return out
 
 
+# --------------------------------------------------- device destinations --
+_KLB_TORCH = {0: "uint8", 1: "uint16", 2: "uint32", 3: "uint64", 4: "int8", 5: "int16", 6: "int32", 7: "int64",
+              8: "float32", 9: "float64"}
+
+
+def _need(name):
+    L = lib()
+    if not hasattr(L, name):
+        raise LfmError("liblfm.so has no %s (built before the device-destination decode)" % name)
+    return getattr(L, name)
+
+
+def _device_header(buf, what):
+    """(xyzct, KLB data type) of an in-memory .lfm, ValueError when it holds no header."""
+    import struct
+    if len(buf) < 43:
+        raise ValueError("%s: %d bytes hold no .lfm header" % (what, len(buf)))
+    head = bytes(memoryview(buf)[:43]) if not isinstance(buf, np.ndarray) else buf[:43].tobytes()
+    dt = head[42]
+    if dt not in _KLB_TORCH:
+        raise ValueError("%s: unknown data type %d in the header" % (what, dt))
+    return list(struct.unpack_from("<5I", head, 2)), dt
+
+
+def _device_out(what, dt, shape, out, device):
+    """The CUDA tensor a device-destination decode writes: `out` checked
+    (contiguous, on a CUDA device, the file's dtype -- int16 stands in for
+    uint16 as in Encoder._operand -- and the size), or a fresh one on `device`.
+    A non-default current stream is synchronised: the library orders its
+    writes after the null stream's work only."""
+    if not _HAVE_TORCH:
+        raise LfmError("%s needs PyTorch" % what)
+    tdt = getattr(torch, _KLB_TORCH[dt])
+    count = int(np.prod(shape))
+    if out is None:
+        if device is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise ValueError("%s: device must be a CUDA device, not %s" % (what, device))
+        out = torch.empty(tuple(shape), dtype=tdt, device=device)
+    else:
+        if not isinstance(out, torch.Tensor) or not out.is_cuda:
+            raise ValueError("%s: out must be a torch CUDA tensor" % what)
+        if not out.is_contiguous():
+            raise ValueError("%s: out must be contiguous (got strides %s)" % (what, out.stride(),))
+        if out.dtype != tdt and not (dt == 1 and out.dtype == torch.int16):
+            raise ValueError("%s: the file holds %s, out is %s" % (what, tdt, out.dtype))
+        if out.numel() != count:
+            raise ValueError("%s: out holds %d elements, the result is %s" % (what, out.numel(), tuple(shape)))
+        if device is not None and torch.device(device).index not in (None, out.device.index):
+            raise ValueError("%s: out lives on %s, not on %s" % (what, out.device, device))
+        out = out.view(tuple(shape))
+    cur = torch.cuda.current_stream(out.device)
+    if cur != torch.cuda.default_stream(out.device):
+        cur.synchronize()
+    return out
+
+
+def decode_device(buf, out=None, device=None, num_threads=-1, return_stats=False):
+    """Decode an in-memory .lfm into device memory (lfm_decode_memory_device):
+    returns a torch CUDA tensor [t, c, z, y, x] in the file's dtype (uint16 for
+    a KLB uint16 file), `out` itself (viewed in that shape) when given; with
+    return_stats also the lfm_decode_stats as a dict.  The library's writes
+    come after the null stream's work on the tensor's device; when the call
+    returns, any stream may read the tensor.  After an LfmError the tensor's
+    contents are unspecified."""
+    fn = _need("lfm_decode_memory_device")
+    xyzct, dt = _device_header(buf, "decode_device")
+    out = _device_out("decode_device", dt, xyzct[::-1], out, device)
+    st = DecodeStats()
+    _check(fn(_addr(buf), len(buf), out.data_ptr(), out.numel() * out.element_size(), num_threads, ctypes.byref(st)),
+           "lfm_decode_memory_device")
+    return (out, st.as_dict()) if return_stats else out
+
+
+def decode_roi_device(buf, lb, ub, out=None, device=None, num_threads=-1, return_stats=False):
+    """Region lb .. ub (inclusive, [x, y, z, c, t]) of an in-memory .lfm into
+    device memory (lfm_decode_memory_roi_device); as decode_device otherwise."""
+    fn = _need("lfm_decode_memory_roi_device")
+    xyzct, dt = _device_header(buf, "decode_roi_device")
+    lb, ub = [int(v) for v in lb], [int(v) for v in ub]
+    if len(lb) != 5 or len(ub) != 5 or any(u < l or l < 0 or u >= d for l, u, d in zip(lb, ub, xyzct)):
+        raise ValueError("decode_roi_device: region %s .. %s lies outside the image %s" % (lb, ub, xyzct))
+    shape = [u - l + 1 for l, u in zip(lb, ub)][::-1]
+    out = _device_out("decode_roi_device", dt, shape, out, device)
+    st = DecodeStats()
+    _check(fn(_addr(buf), len(buf), _u32(lb), _u32(ub), out.data_ptr(), out.numel() * out.element_size(),
+              num_threads, ctypes.byref(st)), "lfm_decode_memory_roi_device")
+    return (out, st.as_dict()) if return_stats else out
+
+
+def read_lfm_device(path, out=None, device=None, num_threads=-1, return_stats=False, family=None):
+    """Read a .lfm file and decode it into device memory (decode_device)."""
+    if family is not None:
+        set_family(family)
+    with open(path, "rb") as f:
+        buf = f.read()
+    return decode_device(buf, out=out, device=device, num_threads=num_threads, return_stats=return_stats)
+
+
 # ------------------------------------------------------ device primitives --
 def _stream(stream):
     if stream is None:
         return None
     return ctypes.c_void_p(int(stream.cuda_stream) if hasattr(stream, "cuda_stream") else int(stream))
+
+
+def crop_device(d_src, src_dims, lb, n, bpp, d_dst, stream=None):
+    """lfm_hip_crop_region: the box lb .. lb + n - 1 ([x, y, z, c, t]) of a device
+    image of src_dims (bpp bytes per sample) into the dense device array d_dst
+    (tensors or raw pointers); asynchronous on `stream`."""
+    fn = _need("lfm_hip_crop_region")
+    p = lambda t: t.data_ptr() if hasattr(t, "data_ptr") else int(t)  # noqa: E731
+    if len(src_dims) != 5 or len(lb) != 5 or len(n) != 5:
+        raise ValueError("crop_device: src_dims, lb and n have five entries")
+    if any(int(v) < 0 or int(v) >= 1 << 32 for v in list(src_dims) + list(lb) + list(n)):
+        raise ValueError("crop_device: extents are 32-bit unsigned")
+    _check(fn(p(d_src), _u32(src_dims), _u32(lb), _u32(n), int(bpp), p(d_dst), _stream(stream)),
+           "lfm_hip_crop_region")
 
 
 def predict_device(d_in, d_out, W, H, nframes, T, family, predictor, video=0, z0=0, d_prev=None, stream=None):
