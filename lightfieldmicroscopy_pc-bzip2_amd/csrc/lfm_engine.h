@@ -12,6 +12,8 @@
 #include <hip/hip_runtime.h>
 #include "klb_imageHeader.h"
 #include "lfm_api.h"
+#include "lfm_buffers.h"
+#include "lfm_transfer.h"
 
 namespace lfm {
 
@@ -208,10 +210,8 @@ private:
         // SDMA copies (HSA async copies, not a blit kernel beside the GPU
         // bzip2): completion signals and, for pageable sources, two pinned
         // staging chunks; kept between encodes
-        uint64_t sig[2] = {0, 0};
-        void* stage[2] = {nullptr, nullptr};
-        size_t stage_cap = 0;
-        void release_sdma();
+        SdmaPair sdma;
+        HostBuffer stage[2];
         // make `st` wait until frames [0, f_end) are predicted (0 or 3)
         int wait_frames(uint64_t f_end, hipStream_t st);
         void join();
@@ -227,7 +227,6 @@ private:
     int preselect(const void* img, bool dev, const klb_image_header& h, const SlabSpec& slab, int* k, float ent[8]);
     int ensure_gpu();
     int after_caller(bool dev);
-    void* dev_alloc(void*& p, size_t& cap, size_t need);
     void join_inflight();
     Inflight fly_[2];                         // by buffer set
     UploadPipe up_[2];                        // by buffer set
@@ -240,23 +239,22 @@ private:
     hipStream_t stream_ = nullptr;
     hipEvent_t ev0_ = nullptr, ev1_ = nullptr;
     hipEvent_t caller_ev_ = nullptr;          // the null stream's work before a device input
-    void* d_in_ = nullptr;  size_t d_in_cap_ = 0;
-    void* d_sym_[2] = {nullptr, nullptr}; size_t d_sym_cap_[2] = {0, 0};  // by buffer set
-    void* d_ws_ = nullptr;  size_t d_ws_cap_ = 0;
-    void* d_prev_ = nullptr; size_t d_prev_cap_ = 0;
-    void* d_sel_ = nullptr; size_t d_sel_cap_ = 0;  // host select_frame uploaded
+    DeviceBuffer d_in_;
+    DeviceBuffer d_sym_[2];  // by buffer set
+    DeviceBuffer d_ws_;
+    DeviceBuffer d_prev_;
+    DeviceBuffer d_sel_;     // host select_frame uploaded
     // GPU bzip2 pipeline slots (stream, workspace, device + pinned output),
     // kBzSlots per buffer set (LFM_BZ2_SLOTS picks how many run, at most that)
     static constexpr int kBzSlots = 4;
     struct BzSlot {
         hipStream_t stream = nullptr;
-        void* d_ws = nullptr; size_t d_ws_cap = 0;
-        void* d_out = nullptr; size_t d_out_cap = 0;
-        void* h_out = nullptr; size_t h_out_cap = 0;
+        DeviceBuffer d_ws, d_out;
+        HostBuffer h_out;
     };
     BzSlot bz_[2][kBzSlots];
     static int bz_slot_count();  // slots that run (env LFM_BZ2_SLOTS, default 2)
-    void* h_sym_[2] = {nullptr, nullptr}; size_t h_sym_cap_[2] = {0, 0};   // pinned, by buffer set
+    HostBuffer h_sym_[2];  // pinned, by buffer set
 };
 
 // process-wide encoders for the C ABI / klb_imageIO, one per (device, worker

@@ -833,18 +833,22 @@ print(json.dumps(out))
 """
 
 
-def test_host_upload_pipe_chunks_and_ring(gpu, tmp_path):
+@pytest.mark.parametrize("extra", [pytest.param("", id="sdma"), "LFM_H2D_SDMA=0", "LFM_D2H_SDMA=0"])
+def test_host_upload_pipe_chunks_and_ring(gpu, tmp_path, extra):
     """Host stacks upload in chunks through a ring of device slots, each chunk
     predicted as it lands and every GPU-bzip2 batch waiting only for its
     chunks (UploadPipe).  With 1-MiB chunks and a 3-slot ring every slot is
     reused: video stacks (temporal predecessors across chunk edges), 5-D
     stacks, an odd-start video slab with its previous frame from the host, and
     pipelined host submits (the stack refilled as soon as submit returns)
-    give the oracle's bytes."""
+    give the oracle's bytes -- with the chunks on an SDMA engine, with the
+    uploader's hipMemcpyAsync loop (LFM_H2D_SDMA=0), and without an HSA agent
+    (LFM_D2H_SDMA=0: the payload comes down with HIP copies too)."""
     import subprocess
     import sys
     from conftest import PKG, REPO
     env = dict(os.environ, LFM_H2D_CHUNK_MB="1", LFM_H2D_RING_MB="2")
+    env.update(kv.split("=", 1) for kv in extra.split())
     r = subprocess.run([sys.executable, "-c", _UPLOAD_CHILD, PKG, os.path.join(REPO, "oracle")], env=env,
                        capture_output=True, text=True, timeout=200)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -904,12 +908,19 @@ def test_submit_select_frame_and_wait_codes(lfmlib, oracle, gpu):
         lfmlib.set_family("tiles")
 
 
-@pytest.mark.parametrize("env", ["LFM_DECODE_H2D=1", "LFM_DECODE_H2D=2"])
+@pytest.mark.parametrize("env", ["LFM_DECODE_H2D=1", "LFM_DECODE_H2D=2", "LFM_DECODE_D2H=0", "LFM_DECODE_D2H=2",
+                                 "LFM_D2H_SDMA=0", "LFM_DECODE_PREFAULT=0",
+                                 "LFM_DECODE_KEEP=0 LFM_DECODE_CHUNK_BLOCKS=1"])
 def test_decode_path_switches(lfmlib, oracle, gpu, tmp_path, env):
     """The decode's fallback payload uploads (one runtime copy, or
     hipMemcpyAsync from the pinned chunks, instead of the SDMA engine) restore
-    the same pixels.  The switches are read once per process: each variant
-    decodes in its own child process (one GPU process at a time)."""
+    the same pixels, and so do its other paths: every chunk's download on an
+    SDMA engine (LFM_DECODE_D2H=0) or by the runtime (2), no HSA agent at all
+    (LFM_D2H_SDMA=0: every SDMA copy falls back to HIP copies), no prefault
+    thread, and buffers released after the call with one slab per chunk (many
+    chunks, the slots' buffers re-made).  The switches are read once per
+    process: each variant decodes in its own child process (one GPU process at
+    a time)."""
     import subprocess
     import sys
     from conftest import PKG
