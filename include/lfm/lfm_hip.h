@@ -87,8 +87,10 @@ int lfm_hip_select(const uint16_t* d_frame, int W, int H, int T, int family, flo
  * back to back in d_payload (block order); h_sizes[i] / h_flags[i] per
  * stream (flag != 0: the stream is NOT in the payload and must be produced by
  * the host library -- RLE1 block reaching nblockMAX, or a periodic block).
- * d_ws: lfm_hip_bzip2_workspace_bytes(count, blockBytes).  Synchronous. */
+ * d_ws: lfm_hip_bzip2_workspace_bytes(count, blockBytes); d_payload: count *
+ * lfm_hip_bzip2_out_cap(blockBytes) bytes.  Synchronous. */
 size_t lfm_hip_bzip2_workspace_bytes(uint32_t count, uint32_t block_bytes);
+size_t lfm_hip_bzip2_out_cap(uint32_t block_bytes);
 int lfm_hip_bzip2_blocks(const void* d_img, const uint32_t dims[5], const uint32_t bs[5], uint32_t bpp,
                          uint32_t first, uint32_t count, uint32_t level, void* d_ws, size_t ws_bytes,
                          void* d_payload, uint64_t* h_sizes, uint32_t* h_flags, void* stream);

@@ -8,30 +8,32 @@
 // published bzip2-1.0.6 algorithm (vendored at src/external/bzip2-1.0.6 of the
 // reference; restated, not copied):
 //
-//   rle1_crc   bzlib.c ADD_CHAR_TO_BLOCK / add_pair_to_block: runs of 4..255
-//              equal bytes -> 4 bytes + (len-4); block CRC (MSB-first
-//              CRC-32, poly 0x04c11db7) over the raw bytes; inUse map.
-//              One workgroup per stream: per-thread chunks, a scan carries
-//              the run state across chunks, CRCs of chunks are combined with
-//              GF(2) shift matrices.
-//   BWT        blocksort.c sorts the cyclic rotations of the RLE1 block (the
-//              order is unique for a non-periodic block, so any correct sort
-//              gives libbzip2's bytes): prefix doubling -- rotations sorted by
-//              their first 8 bytes, then by (rank[i], rank[i+h]) for h = 8,
-//              16, ... with segmented radix sorts (one segment per stream)
-//              until every rank is unique.  A periodic block (equal
-//              rotations) is handed back to the host library.
-//   mtf        compress.c generateMTFValues: move-to-front + RUNA/RUNB zero
-//              runs, one wave per stream, the 256-entry list packed 4 bytes
-//              per lane, lookups by ballot.
-//   huffman    compress.c sendMTFValues + huffman.c: table count by nMTF,
-//              initial partition, 4 refinement passes (selector per 50
-//              symbols: first minimum cost; BZ2_hbMakeCodeLengths with
-//              maxLen 17 and its weight-halving retry), selector MTF, codes.
-//   emit       the bit stream: "BZh" + level, block magic, CRC, origPtr,
-//              mapping table, selectors, delta-coded lengths, the symbols,
-//              end magic and combined CRC; MSB-first bits.  Symbol codes are
-//              written by all threads at prefix-summed bit offsets.
+//   rle1    gather_blocks, rle1_crc: bzlib.c ADD_CHAR_TO_BLOCK / add_pair_to_block:
+//           runs of 4..255 equal bytes -> 4 bytes + (len-4); block CRC
+//           (MSB-first CRC-32, poly 0x04c11db7) over the raw bytes; inUse map.
+//           One workgroup per stream: per-thread chunks, a scan carries the
+//           run state across chunks, CRCs of chunks are combined with GF(2)
+//           shift matrices.
+//   BWT     blocksort.c sorts the cyclic rotations of the RLE1 block (the
+//           order is unique for a non-periodic block, so any correct sort
+//           gives libbzip2's bytes).  Two stages: the rotations of one type
+//           are sorted (bwt_bucket, chunk sorts by the 8-byte prefix, text
+//           rounds over what still ties; prefix doubling over every rotation
+//           only for long repeats), the others placed by one induction scan
+//           (bwt_place_sorted, bwt_induce).  A periodic block (equal
+//           rotations) is handed back to the host library.
+//   mtf     compress.c generateMTFValues: move-to-front per 4096-symbol
+//           segment (mtf_last, mtf_prefix, mtf_win), then RUNA/RUNB zero runs
+//           and the symbol frequencies (rle2).
+//   huffman compress.c sendMTFValues + huffman.c: table count by nMTF,
+//           initial partition, 4 refinement passes (selector per 50
+//           symbols: first minimum cost; BZ2_hbMakeCodeLengths with
+//           maxLen 17 and its weight-halving retry), selector MTF, codes.
+//   emit    the bit stream: "BZh" + level, block magic, CRC, origPtr,
+//           mapping table, selectors, delta-coded lengths, the symbols,
+//           end magic and combined CRC; MSB-first bits.  Symbol codes are
+//           written by all threads at prefix-summed bit offsets; the streams
+//           are then compacted into the payload.
 //
 // Streams whose RLE1 block reaches nblockMAX (libbzip2 would cut a second
 // block) or that are periodic are flagged for the host library: the output
@@ -50,9 +52,15 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
+#include <mutex>
+#include <type_traits>
 #include <vector>
+#include "lfm_bz_caps.h"  // rle_cap, out_cap, sel_cap, kGSize, align_up
 #include "lfm_hip.h"
 
+#ifndef LFM_BWT_FORCE_FULL
+#define LFM_BWT_FORCE_FULL 0  // timing variants: every rotation sorted, no induction
+#endif
 
 namespace lfm {
 namespace bz {
@@ -60,14 +68,11 @@ namespace bz {
 constexpr int kRleThreads = 512;
 constexpr int kMaxGroups = 6;
 constexpr int kMaxAlpha = 258;
-constexpr int kGSize = 50;
 constexpr int kIters = 4;
 constexpr uint32_t kRunA = 0, kRunB = 1;
 
 // flags
 constexpr uint32_t kFlagHost = 1;  // compress this stream with the host library
-
-__constant__ uint32_t c_crc_table[256];
 
 struct Geometry {
     uint32_t dims[5];   // x y z c t
@@ -132,8 +137,6 @@ struct Batch {
     uint2* ent;              // bwt_induce's entries per final position (the keys_a area, free after the sorts)
     uint32_t it_full;        // sort every rotation (no induction): the fallback for ties that need doubling
 };
-
-__device__ __forceinline__ uint32_t crc_feed(uint32_t c, uint32_t b) { return (c << 8) ^ c_crc_table[(c >> 24) ^ b]; }
 
 // ------------------------------------------------------------- gather --
 // Block id -> origin/size, x fastest (klb_imageIO.cpp:133-140); the block's
@@ -221,20 +224,6 @@ __device__ __forceinline__ RunSum run_shfl_up(const RunSum& a, int d)
     r.lead = __shfl_up(a.lead, d);
     r.trail = __shfl_up(a.trail, d);
     return r;
-}
-
-// Visit the bytes p[0 .. len) in order with 16-byte loads (p 16-byte aligned;
-// the load may read up to 15 bytes past len, inside the stream's buffer).
-template <typename F>
-__device__ __forceinline__ void for_bytes(const uint8_t* p, uint32_t len, F&& f)
-{
-    for (uint32_t k = 0; k < len; k += 16) {
-        const uint4 v = *(const uint4*)(p + k);
-        const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-        for (uint32_t b = 0; b < 16; ++b)
-            if (k + b < len) f((w[b >> 2] >> (8 * (b & 3))) & 0xFFu);
-    }
 }
 
 constexpr uint32_t kRleChunk = 32;
@@ -577,9 +566,6 @@ __global__ __launch_bounds__(kRleThreads) __attribute__((amdgpu_waves_per_eu(4))
 // preceding it (bits 24-31): after sorting, that byte IS the BWT output
 // column, so the MTF stage reads it in sorted order without a gather.
 constexpr uint32_t kIdxMask = 0x00FFFFFFu;
-#ifndef LFM_BWT_PACK
-#define LFM_BWT_PACK 0  // 1: bwt_chunk_sort sorts (key - min) << LJ | slot keys only where the range allows (measured no faster)
-#endif
 constexpr uint32_t kKeyBytes = 8;  // first-round key: the 8-byte prefix (0.02 % of rotations tie on symbols)
 
 // First round: every rotation by its 8-byte prefix, in two steps.
@@ -1129,92 +1115,31 @@ __global__ __launch_bounds__(TH) void bwt_chunk_sort(Batch B, const uint32_t* __
     if (c >= nch) return;
     static_assert(IPT == 2 || IPT == 4 || IPT == 8, "flags are packed 2, 4 or 8 per thread");
     using Sort = rocprim::block_sort<uint64_t, TH, IPT, uint32_t, rocprim::block_sort_algorithm::merge_sort>;
-    using SortK = rocprim::block_sort<uint64_t, TH, IPT, rocprim::empty_type, rocprim::block_sort_algorithm::merge_sort>;
     using ExK = rocprim::block_exchange<uint64_t, TH, IPT>;
     using ExV = rocprim::block_exchange<uint32_t, TH, IPT>;
-    constexpr uint32_t NI = TH * IPT, NW = TH / 64;
+    constexpr uint32_t NI = TH * IPT;
     struct Xch {
         uint64_t first[TH], last[TH];
         uint32_t sv[NI];
         uint8_t fl[NI];
     };
-    struct Packed {
-        typename SortK::storage_type s;
-        uint32_t sv[NI];  // the values by load slot
-    };
     __shared__ union alignas(16) {
         typename Sort::storage_type s;
         typename ExK::storage_type ek;
         typename ExV::storage_type ev;
-        Packed pk;
         Xch x;
     } sm;
     const uint32_t cb = cbp[c], ce = cep[c], m = ce - cb, t = threadIdx.x;
     uint64_t k[IPT];
     uint32_t v[IPT];
     chunk_load<TH, IPT>(B, cb, m, t, k, v);
-    bool packed = false;
-#if LFM_BWT_PACK
-    // Keys only when they fit: the chunk's key range below 2^(64 - LJ), LJ
-    // the bits of a load slot j < m, sorts (k - kmin) << LJ | j as one 64-bit
-    // key (a third less to move per merge step than key + value; slots past m
-    // get ~0, above every packed key, so the whole tile is sorted without a
-    // valid count or a striped-to-blocked exchange); the values come back
-    // through LDS by slot.
-    {
-        __shared__ uint64_t wlo[NW], whi[NW];
-        uint64_t lo = ~0ull, hi = 0;
-#pragma unroll
-        for (int q = 0; q < IPT; ++q)
-            if (q * TH + t < m) {
-                lo = min(lo, k[q]);
-                hi = max(hi, k[q]);
-            }
-        for (int d = 32; d > 0; d >>= 1) {
-            lo = min(lo, (uint64_t)__shfl_xor(lo, d));
-            hi = max(hi, (uint64_t)__shfl_xor(hi, d));
-        }
-        if ((t & 63) == 0) {
-            wlo[t >> 6] = lo;
-            whi[t >> 6] = hi;
-        }
-        __syncthreads();
-#pragma unroll
-        for (uint32_t x = 0; x < NW; ++x) {
-            lo = min(lo, wlo[x]);
-            hi = max(hi, whi[x]);
-        }
-        const uint32_t LJ = 32u - (uint32_t)__builtin_clz(max(m, 2u) - 1u);
-        if (((hi - lo) >> (64u - LJ)) == 0) {
-            packed = true;
-#pragma unroll
-            for (int q = 0; q < IPT; ++q) {
-                const uint32_t j = q * TH + t;
-                if (j < m) sm.pk.sv[j] = v[q];
-                k[q] = j < m ? ((k[q] - lo) << LJ) | j : ~0ull;
-            }
-            SortK().sort(k, sm.pk.s);
-            __syncthreads();
-            const uint64_t jm = (1ull << LJ) - 1ull;
-#pragma unroll
-            for (int q = 0; q < IPT; ++q) {
-                const uint32_t pos = t * IPT + q;
-                v[q] = pos < m ? sm.pk.sv[(uint32_t)(k[q] & jm)] : 0u;
-                k[q] >>= LJ;  // (the tie flags compare these; positions >= m are never compared)
-            }
-            __syncthreads();
-        }
-    }
-#endif
-    if (!packed) {
-        // the sort's valid-item count refers to the blocked arrangement
-        ExK().striped_to_blocked(k, k, sm.ek);
-        __syncthreads();
-        ExV().striped_to_blocked(v, v, sm.ev);
-        __syncthreads();
-        Sort().sort(k, v, sm.s, m);
-        __syncthreads();
-    }
+    // the sort's valid-item count refers to the blocked arrangement
+    ExK().striped_to_blocked(k, k, sm.ek);
+    __syncthreads();
+    ExV().striped_to_blocked(v, v, sm.ev);
+    __syncthreads();
+    Sort().sort(k, v, sm.s, m);
+    __syncthreads();
     sm.x.first[t] = k[0];
     sm.x.last[t] = k[IPT - 1];
     __syncthreads();
@@ -1246,149 +1171,6 @@ __global__ __launch_bounds__(TH) void bwt_chunk_sort(Batch B, const uint32_t* __
     if (__any(nt)) {
         for (int d = 32; d > 0; d >>= 1) nt += __shfl_xor(nt, d);
         if ((threadIdx.x & 63) == 0 && nt) atomicAdd(&B.done[cb / B.cap], nt);
-    }
-}
-
-// bwt_chunk_rsort: bwt_chunk_sort's contract (a chunk's rotations ordered by
-// their 8-byte big-endian prefix into sa, the still-tied flags into uflag and
-// B.done) as a hand-written LDS radix sort, least significant digit first,
-// over only the key bits that vary inside the chunk: D = OR(k) & ~AND(k) over
-// its keys, and each pass takes the 8-bit digit at s, the next one at the
-// lowest varying bit >= s + 8.  Bits constant across the chunk -- the
-// bucket's leading bits, the zero high bits of small symbols' bytes -- cost no
-// pass.  Ranking: a wave finds the lanes sharing an item's digit with 8
-// ballots, keeps a running count per (digit, wave) in LDS, and one exclusive
-// scan over the digit-major (digit, wave) counts gives every digit's start.
-// Positions are ordered by wave, then item, then lane, so each pass is stable
-// as LSD needs.  The order of equal keys is free (tie_runs_direct and the tie
-// rounds order them), so the first pass ranks the items as loaded.
-template <int TH, int IPT>
-__global__ __launch_bounds__(TH) void bwt_chunk_rsort(Batch B, const uint32_t* __restrict__ cbp,
-                                                      const uint32_t* __restrict__ cep, uint32_t nch, uint32_t per)
-{
-    const uint32_t c = per ? (blockIdx.x & 7u) * per + (blockIdx.x >> 3) : blockIdx.x;  // (XCD order, as bwt_chunk_sort)
-    if (c >= nch) return;
-    constexpr uint32_t NW = TH / 64, NI = TH * IPT, WI = 64 * IPT;
-    static_assert(256 * NW == 4 * TH, "four (digit, wave) counters per thread");
-    __shared__ uint64_t sk[NI];
-    __shared__ uint32_t sv[NI];
-    __shared__ uint32_t hist[256 * NW];  // [digit][wave]
-    __shared__ uint32_t wsum[NW];
-    __shared__ uint64_t wor[NW], wand[NW];
-    const uint32_t cb = cbp[c], ce = cep[c], m = ce - cb, t = threadIdx.x, lane = t & 63, w = t >> 6;
-    uint64_t k[IPT];
-    uint32_t v[IPT];
-    chunk_load<TH, IPT>(B, cb, m, t, k, v);
-    {  // the varying bits
-        uint64_t o = 0, a = ~0ull;
-#pragma unroll
-        for (int q = 0; q < IPT; ++q)
-            if (q * TH + t < m) {
-                o |= k[q];
-                a &= k[q];
-            }
-        for (int d = 32; d > 0; d >>= 1) {
-            o |= __shfl_xor(o, d);
-            a &= __shfl_xor(a, d);
-        }
-        if (lane == 0) {
-            wor[w] = o;
-            wand[w] = a;
-        }
-#pragma unroll
-        for (int e = 0; e < 4; ++e) hist[4 * t + e] = 0;
-    }
-    __syncthreads();
-    uint64_t D = 0, A = ~0ull;
-#pragma unroll
-    for (uint32_t x = 0; x < NW; ++x) {
-        D |= wor[x];
-        A &= wand[x];
-    }
-    D &= ~A;
-    const uint64_t lt = (1ull << lane) - 1ull;
-    bool first = true;
-    for (uint32_t s = D ? (uint32_t)__builtin_ctzll(D) : 64u; s < 64u;) {
-        uint32_t r[IPT], dg[IPT];
-#pragma unroll
-        for (int q = 0; q < IPT; ++q) {
-            const bool ok = first ? q * TH + t < m : w * WI + q * 64 + lane < m;
-            const uint32_t d = (uint32_t)(k[q] >> s) & 0xFFu;
-            uint64_t same = __ballot(ok);
-#pragma unroll
-            for (int b = 0; b < 8; ++b) {  // keep the lanes whose bit b equals this lane's
-                const int32_t e = (int32_t)(d << (31 - b)) >> 31;  // 0 / -1
-                const uint64_t bb = __ballot(e != 0);
-                same &= ~(bb ^ (uint64_t)(int64_t)e);
-            }
-            const uint32_t below = __popcll(same & lt);
-            uint32_t* h = &hist[d * NW + w];
-            const uint32_t base = ok ? *h : 0u;
-            if (ok && below == 0) *h = base + __popcll(same);
-            r[q] = ok ? base + below : ~0u;
-            dg[q] = d;
-        }
-        __syncthreads();
-        {  // exclusive scan of the counts, digit-major
-            const uint32_t x0 = hist[4 * t], x1 = hist[4 * t + 1], x2 = hist[4 * t + 2], x3 = hist[4 * t + 3];
-            const uint32_t sum = x0 + x1 + x2 + x3;
-            uint32_t inc = sum;
-            for (int d = 1; d < 64; d <<= 1) {
-                const uint32_t y = __shfl_up(inc, d);
-                if ((int)lane >= d) inc += y;
-            }
-            if (lane == 63) wsum[w] = inc;
-            __syncthreads();
-            uint32_t p = inc - sum;
-            for (uint32_t x = 0; x < w; ++x) p += wsum[x];
-            hist[4 * t] = p;
-            hist[4 * t + 1] = p + x0;
-            hist[4 * t + 2] = p + x0 + x1;
-            hist[4 * t + 3] = p + x0 + x1 + x2;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int q = 0; q < IPT; ++q)
-            if (r[q] != ~0u) {
-                const uint32_t to = hist[dg[q] * NW + w] + r[q];
-                sk[to] = k[q];
-                sv[to] = v[q];
-            }
-        __syncthreads();
-#pragma unroll
-        for (int q = 0; q < IPT; ++q) {
-            const uint32_t p = w * WI + q * 64 + lane;
-            k[q] = sk[p];
-            v[q] = sv[p];
-        }
-        // this wave's counters back to zero (every wave has read its
-        // digits' starts before the barrier; only this wave counts into them)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) hist[(lane + 64 * e) * NW + w] = 0;
-        first = false;
-        const uint64_t rest = s + 8u < 64u ? D >> (s + 8u) : 0ull;
-        s = rest ? s + 8u + (uint32_t)__builtin_ctzll(rest) : 64u;
-    }
-    if (first) {  // every key equal: no pass ran, the items as loaded
-#pragma unroll
-        for (int q = 0; q < IPT; ++q)
-            if (q * TH + t < m) {
-                sk[q * TH + t] = k[q];
-                sv[q * TH + t] = v[q];
-            }
-        __syncthreads();
-    }
-    uint32_t nt = 0;
-    for (uint32_t j = t; j < m; j += TH) {
-        const uint64_t kj = sk[j];
-        const bool f = (j > 0 && sk[j - 1] == kj) || (j + 1 < m && sk[j + 1] == kj);
-        B.sa[cb + j] = sv[j];
-        B.uflag[cb + j] = f ? 1 : 0;
-        nt += f ? 1u : 0u;
-    }
-    if (__any(nt)) {
-        for (int d = 32; d > 0; d >>= 1) nt += __shfl_xor(nt, d);
-        if (lane == 0 && nt) atomicAdd(&B.done[cb / B.cap], nt);
     }
 }
 
@@ -2279,15 +2061,10 @@ __device__ __forceinline__ uint64_t wave_or_scan_excl(uint64_t x)
     return ((uint64_t)wave_or_scan_excl32((uint32_t)(x >> 32)) << 32) | wave_or_scan_excl32((uint32_t)x);
 }
 
-#ifndef LFM_MTF_BALLOT
-#define LFM_MTF_BALLOT 0  // 1: mtf_win's match masks by eight ballots instead of LDS atomicOr (measured slower)
-#endif
 __global__ __launch_bounds__(256) void mtf_win(Batch B, uint32_t nseg_max, const int32_t* __restrict__ seg_last)
 {
     __shared__ int32_t key[4][256];
-#if !LFM_MTF_BALLOT
     __shared__ uint64_t mt[4][256];
-#endif
     __shared__ uint8_t Pt[4][256], Lt[4][256], inw[4][256];
     const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const uint32_t s = blockIdx.y, k = blockIdx.x * 4 + wave;
@@ -2329,24 +2106,11 @@ __global__ __launch_bounds__(256) void mtf_win(Batch B, uint32_t nseg_max, const
         const uint32_t c = valid ? cn : 0u;
         cn = llbuf[min(j + 64, je - 1)];
         // match mask of c in this window
-#if LFM_MTF_BALLOT
-        // eight ballots, one per bit of c: the lanes whose byte equals this
-        // lane's (VALU and scalar masks only; the LDS atomicOr per lane
-        // serialised on the long runs of one byte in the BWT output)
-        uint64_t M = ballot64(valid);
-#pragma unroll
-        for (int b = 0; b < 8; ++b) {
-            const int32_t e = (int32_t)(c << (31 - b)) >> 31;  // 0 / -1
-            M &= ~(ballot64(e != 0) ^ (uint64_t)(int64_t)e);
-        }
-        M = valid ? M : 0ull;
-#else
         if (valid) mt[wave][c] = 0;
         wsync();
         if (valid) atomicOr((unsigned long long*)&mt[wave][c], 1ull << lane);
         wsync();
         const uint64_t M = valid ? mt[wave][c] : 0ull;
-#endif
         const uint64_t before = M & lt;
         const bool has_prev = before != 0ull;
         const uint32_t p_in = has_prev ? 63u - (uint32_t)__clzll(before) : 0u;
@@ -2476,14 +2240,7 @@ __device__ __forceinline__ uint64_t zero_byte_mask64(const uint32_t (&q)[kRle2Pe
 // bits with its 32-word row number spreads them over the banks; rows stay
 // whole, so the coalesced read-out (consecutive indices) is a permutation
 // inside each row, conflict-free as well.
-#ifndef LFM_RLE2_SWZ
-#define LFM_RLE2_SWZ 1
-#endif
-__device__ __forceinline__ uint32_t rle2_swz(uint32_t p)
-{
-    if constexpr (LFM_RLE2_SWZ) return p ^ (((p >> 6) & 31u) << 1);
-    else return p;
-}
+__device__ __forceinline__ uint32_t rle2_swz(uint32_t p) { return p ^ (((p >> 6) & 31u) << 1); }
 
 __global__ __launch_bounds__(kRle2Threads) __attribute__((amdgpu_waves_per_eu(4))) void rle2(Batch B)
 {
@@ -3495,11 +3252,10 @@ uint32_t host_crc4[4][256];
 uint32_t host_crc_shift[kCrcLevels][32];
 uint32_t host_crc_unshift[kCrcUnshift][32];
 uint32_t host_crc_shb[kCrcLevels][4][256];  // host_crc_shift as byte tables
-bool crc_ready = false;
 
-void ensure_crc_table()
+// runs once per process (crc_tables_on_device)
+bool build_crc_tables()
 {
-    if (crc_ready) return;
     for (uint32_t i = 0; i < 256; ++i) {
         uint32_t c = i << 24;
         for (int k = 0; k < 8; ++k) c = (c & 0x80000000u) ? (c << 1) ^ 0x04c11db7u : (c << 1);
@@ -3549,10 +3305,29 @@ void ensure_crc_table()
             for (uint32_t v = 0; v < 256; ++v) host_crc_shb[l][j][v] = mat_apply(host_crc_shift[l], v << (8 * j));
     for (int k = 0; k < 32; ++k) host_crc_unshift[0][k] = unfeed0(1u << k);
     for (int l = 1; l < kCrcUnshift; ++l) mat_square(host_crc_unshift[l - 1], host_crc_unshift[l]);
-    crc_ready = true;
+    return true;
 }
 
-size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+// Every caller passes here before its first rle1_crc launch on `dev` (the
+// current device): the first one uploads, under the mutex, so a later caller
+// returns only once the tables are there; nobody writes them again while
+// another stream's rle1_crc may be reading them.
+bool crc_tables_on_device(int dev)
+{
+    static const bool built = build_crc_tables();  // function-local static: once, thread-safely
+    static std::mutex mu;
+    static std::vector<char> uploaded;  // per device
+    std::lock_guard<std::mutex> lock(mu);
+    if (!built || dev < 0) return false;
+    if ((size_t)dev >= uploaded.size()) uploaded.resize((size_t)dev + 1, 0);
+    if (uploaded[dev]) return true;
+    if (hipMemcpyToSymbol(HIP_SYMBOL(c_crc4), host_crc4, sizeof(host_crc4)) != hipSuccess ||
+        hipMemcpyToSymbol(HIP_SYMBOL(c_crc_shb), host_crc_shb, sizeof(host_crc_shb)) != hipSuccess ||
+        hipMemcpyToSymbol(HIP_SYMBOL(c_crc_unshift), host_crc_unshift, sizeof(host_crc_unshift)) != hipSuccess)
+        return false;
+    uploaded[dev] = 1;
+    return true;
+}
 
 // stage boundary events of the calling thread (lfm_hip_bzip2_last_stage_ms)
 struct StageEvents {
@@ -3608,35 +3383,313 @@ size_t prim_tmp_bytes(uint32_t count, uint32_t cap)
     return tmp;
 }
 
+// The parts of the workspace that are not per-stream kernel buffers.
+// cnt: eight device counters, zeroed at the start of every BWT attempt:
+//   [0]    chunks of class 0 (<= kSmallCap) from the bucket pass; from
+//          tie_offsets on, the length of the tied list (rewritten by every
+//          round's compaction)
+//   [1]    chunks of class 1 (<= kBigCap); then the length of the compacted
+//          group keys of a text round
+//   [2]    chunks of class 2 (rocPRIM segmented sort)
+//   [3]    streams whose Huffman heaps need u64 entries (rle2; Batch::wide_cnt)
+//   [4]    Huffman code-length retries (statistics only)
+//   [5]    chunks of class 3 (<= kTinyCap)
+//   [6]    unused
+//   [7]    tied runs tie_runs_direct left to the tie rounds
+struct Scratch {
+    uint64_t* offs;    // nstreams + 1 byte offsets of the compacted streams
+    uint32_t* cnt;     // the counters above (right after offs)
+    void* tmp;         // rocPRIM temporary storage (prim_tmp_bytes)
+    size_t tmp_bytes;
+};
+
+// What LFM_BZ2_STATS=1 reports about the BWT
+struct BwtStats {
+    uint32_t first_ties = 0;  // tied slots after the chunk sorts
+    uint32_t left_runs = 0;   // runs tie_runs_direct left
+};
+
+// The workspace, described once: every buffer in order, 256-byte aligned.
+// With base == nullptr this only sums (lfm_hip_bzip2_workspace_bytes); with
+// the workspace base it also points B and S into it.  Either way it sets the
+// capacities of B the sizes derive from.  Returns the bytes needed.
+size_t layout(uint8_t* base, uint32_t count, uint32_t block_bytes, Batch& B, Scratch& S)
+{
+    B.nstreams = count;
+    B.raw_cap = (uint32_t)align_up(block_bytes, 16);  // stream stride of the raw blocks (16-byte loads)
+    B.cap = rle_cap(block_bytes);
+    B.out_cap = out_cap(block_bytes);
+    B.sel_cap = sel_cap(block_bytes);
+    const size_t n = count, N = n * B.cap;
+    size_t off = 0;
+    auto take = [&](auto*& p, size_t bytes) {
+        using P = std::remove_reference_t<decltype(p)>;
+        p = base ? (P)(base + off) : nullptr;
+        off += align_up(bytes, 256);
+    };
+    take(B.raw, n * B.raw_cap);
+    take(B.T, N);
+    take(B.keys_a, N * 8);
+    take(B.keys_b, N * 8);
+    take(B.vals_a, N * 4);
+    take(B.sa, N * 4);
+    take(B.rank, N * 4);
+    take(B.vals_b, N * 4);
+    take(B.cl0, N * 4);
+    take(B.cl1, N * 4);
+    take(B.uflag, N);
+    take(B.mtfv, n * (B.cap + 8) * 2);
+    take(B.sel, n * B.sel_cap);
+    take(B.sel_mtf, n * B.sel_cap);
+    take(B.len, n * kMaxGroups * kMaxAlpha);
+    take(B.code, n * kMaxGroups * kMaxAlpha * 4);
+    take(B.rfreq, n * kMaxGroups * kMaxAlpha * 4);
+    take(B.words, n * B.out_cap);
+    take(B.mtf_freq, n * kMaxAlpha * 4);
+    take(B.inuse, n * 8 * 4);
+    take(B.wide, n * kMaxGroups * 4 + 64);
+    take(B.abcnt, n * 512 * 4);
+    take(B.itab, n * 1024 * 4);
+    // one u32 per stream each
+    uint32_t** small[] = {&B.raw_len, &B.n, &B.crc, &B.flags, &B.done, &B.seg_begin, &B.seg_end, &B.nmtf,
+                          &B.orig_ptr, &B.nsel, &B.ngroups, &B.out_bytes, &B.nsub, &B.bwt_mode};
+    for (uint32_t** q : small) take(*q, n * 4 + 64);
+    // pad: two more such arrays that nothing uses.  The engine sizes its
+    // batches from the total, so the total stays what it has always been.
+    off += 2 * align_up(n * 4 + 64, 256);
+    take(S.offs, (n + 1) * 8 + 32);  // the offsets, then the 8 counters
+    S.cnt = base ? (uint32_t*)(S.offs + n + 1) : nullptr;
+    B.wide_cnt = base ? S.cnt + 3 : nullptr;
+    S.tmp_bytes = prim_tmp_bytes(count, B.cap);
+    take(S.tmp, S.tmp_bytes);
+    return off;
+}
+
+// What the steps of one bwt_sort call share.  The tied list (slots whose
+// rotations still compare equal) lives in `cl`, its length in cnt[0] on the
+// device (slot map at Scratch); every round compacts
+// it into cl_next and swaps the two.
+struct TieRounds {
+    hipStream_t st;
+    size_t N;            // nstreams * cap
+    uint32_t* cnt;       // device counters
+    void* tmp;           // rocPRIM temporary storage
+    size_t tmp_bytes;
+    uint32_t* cl;
+    uint32_t* cl_next;
+    uint32_t covered;    // bytes of every rotation the order so far accounts for
+    bool none_left;      // a count read 0 and no kernel ran since: skip the later reads
+    BwtStats stats;
+    uint64_t* gk;        // text rounds' group keys: u64 per entry in the rank area, free until the ranks are built
+
+    // the tied list's length, read back: one host synchronisation
+    hipError_t read_count(uint32_t* out, size_t bytes = 4)
+    {
+        hipError_t e = hipMemcpyAsync(out, cnt, bytes, hipMemcpyDeviceToHost, st);
+        return e != hipSuccess ? e : hipStreamSynchronize(st);
+    }
+};
+
+uint32_t list_grid(uint32_t cnt) { return std::min<uint32_t>(4096, (cnt + 255) / 256); }
+
+// the nc chunks of class `cls`, in XCD-aware order: workgroup b runs on XCD b % 8
+template <int TH, int IPT>
+void chunk_sorts(const Batch& B, const ChunkLists& CL, int cls, uint32_t nc, hipStream_t st)
+{
+    const uint32_t per = (nc + 7) / 8;
+    if (nc) hipLaunchKernelGGL((bwt_chunk_sort<TH, IPT>), dim3(8 * per), dim3(TH), 0, st, B, CL.b[cls], CL.e[cls], nc, per);
+}
+
+// Round 0: the bucket pass, the chunk sorts by the 8-byte prefix (one host
+// synchronisation between them, for the chunk counts), then the tied list
+// and the runs short enough to order directly.
+hipError_t first_round(const Batch& B, TieRounds& W)
+{
+    hipStream_t st = W.st;
+    const uint32_t count = B.nstreams;
+    hipError_t e;
+    ChunkLists CL;
+    const size_t q = W.N / 4;  // chunk lists in the cl0 / cl1 areas (at most 3 n / kChunk + 1 chunks per stream)
+    for (int c = 0; c < 4; ++c) {
+        CL.b[c] = B.cl0 + c * q;
+        CL.e[c] = B.cl1 + c * q;
+    }
+    CL.cnt = W.cnt;
+    CL.cnt3 = W.cnt + 5;
+    uint32_t nch[6] = {0, 0, 0, 0, 0, 0};
+    if ((e = hipMemsetAsync(W.cnt, 0, 32, st)) != hipSuccess ||
+        (e = hipMemsetAsync(B.done, 0, (size_t)count * 4, st)) != hipSuccess)
+        return e;
+    hipLaunchKernelGGL(bwt_bucket<kBucketBits>, dim3(count), dim3(kBucketThreads), 0, st, B, CL);
+    if ((e = hipGetLastError()) != hipSuccess || (e = W.read_count(nch, 24)) != hipSuccess) return e;
+    chunk_sorts<kTinyCap / kCsItems, kCsItems>(B, CL, 3, nch[5], st);
+    chunk_sorts<kCsThreads, kCsItems>(B, CL, 0, nch[0], st);
+    chunk_sorts<kBigThreads, kBigItems>(B, CL, 1, nch[1], st);
+    if (nch[2]) {
+        hipLaunchKernelGGL(bwt_chunk_keys, dim3(nch[2]), dim3(256), 0, st, B, CL.b[2], CL.e[2]);
+        e = rocprim::segmented_radix_sort_pairs(W.tmp, W.tmp_bytes, B.keys_a, B.keys_b, B.vals_a, B.sa,
+                                                (unsigned)W.N, nch[2], CL.b[2], CL.e[2], 0, 64 - kBucketBits, st);
+        if (e == hipSuccess)
+            hipLaunchKernelGGL(bwt_chunk_flags, dim3(nch[2]), dim3(256), 0, st, B, CL.b[2], CL.e[2]);
+    }
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    W.cl = B.cl0;
+    W.cl_next = B.cl1;
+    hipLaunchKernelGGL(tie_offsets, dim3(1), dim3(1024), 0, st, B, W.cnt);
+    hipLaunchKernelGGL(tie_compact, dim3(count), dim3(256), 0, st, B, B.cl0);
+    hipLaunchKernelGGL(tie_runs_direct, dim3(1024), dim3(256), 0, st, B, B.cl0, W.cnt, W.cnt + 7);
+    W.covered = kKeyBytes;
+    W.none_left = false;
+    return hipGetLastError();
+}
+
+// Text rounds over the tied list (group index / bounds in the mtfv area,
+// free here); each starts with a read of the list's length.  Leaves
+// none_left set when a read found nothing to do.
+hipError_t text_rounds(const Batch& B, TieRounds& W)
+{
+    hipStream_t st = W.st;
+    uint32_t* bnd = (uint32_t*)B.mtfv;
+    for (int r = 0; r < kTextRounds; ++r) {
+        // counters: [0] tied slots, [7] runs tie_runs_direct left (read with the first round's count)
+        uint32_t c8[8] = {};
+        hipError_t e = W.read_count(c8, r == 0 ? 32 : 4);
+        if (e != hipSuccess) return e;
+        const uint32_t cnt = c8[0];
+        if (r == 0) {
+            W.stats.first_ties = cnt;
+            W.stats.left_runs = c8[7];
+        }
+        if (cnt == 0 || (r == 0 && c8[7] == 0)) {  // nothing tied, or tie_runs_direct sorted every run
+            W.none_left = true;
+            break;
+        }
+        if ((size_t)cnt * 4 > W.N) break;
+        unsigned gbits = 1;
+        while ((1u << gbits) < cnt) ++gbits;
+        // group index above the text bytes in one 64-bit key: fewer text
+        // bytes when the tied list is longer than 2^24
+        const uint32_t tb = std::min<uint32_t>(kTextBytes, (64 - gbits) / 8);
+        uint32_t* gidx = bnd + cnt;
+        const uint32_t grid = list_grid(cnt);
+        if (r == 0) hipLaunchKernelGGL(text_gather_keys, dim3(grid), dim3(256), 0, st, B, W.cl, W.cnt, W.gk);
+        hipLaunchKernelGGL(text_bounds, dim3(grid), dim3(256), 0, st, B, W.cl, W.cnt, W.gk, bnd);
+        e = rocprim::inclusive_scan(W.tmp, W.tmp_bytes, bnd, gidx, (size_t)cnt, rocprim::plus<uint32_t>(), st);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(text_keys, dim3(grid), dim3(256), 0, st, B, W.cl, W.cnt, gidx, W.covered, tb);
+        e = rocprim::radix_sort_pairs(W.tmp, W.tmp_bytes, B.keys_a, B.keys_b, B.vals_a, B.vals_b, cnt, 0,
+                                      8 * tb + gbits, st);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(text_write, dim3(grid), dim3(256), 0, st, B, W.cl, W.cnt);
+        W.covered += tb;
+        e = rocprim::select(W.tmp, W.tmp_bytes, B.keys_b, B.uflag, W.gk, W.cnt + 1, (size_t)cnt, st);
+        if (e == hipSuccess) e = rocprim::select(W.tmp, W.tmp_bytes, W.cl, B.uflag, W.cl_next, W.cnt, (size_t)cnt, st);
+        if (e != hipSuccess) return e;
+        std::swap(W.cl, W.cl_next);
+    }
+    return hipSuccess;
+}
+
+// Ranks of every rotation for doubling (only with every rotation sorted):
+// group bounds of the remaining `cnt` tied slots from the last text keys, or
+// from the first-round keys when no text round ran.
+hipError_t rank_rebuild(const Batch& B, TieRounds& W, uint32_t cnt)
+{
+    hipStream_t st = W.st;
+    hipError_t e = hipSuccess;
+    uint64_t* gsrc = W.gk;
+    const uint32_t grid = list_grid(cnt);
+    if (W.covered == kKeyBytes) gsrc = (uint64_t*)B.vals_b;  // cnt * 8 <= N * 4 when cnt <= N / 2: rank0 otherwise
+    if (W.covered == kKeyBytes && (size_t)cnt * 2 > W.N) {
+        hipLaunchKernelGGL(bwt_rank0, dim3(B.nstreams), dim3(1024), 0, st, B);
+    } else {
+        if (W.covered == kKeyBytes)
+            hipLaunchKernelGGL(text_gather_keys, dim3(grid), dim3(256), 0, st, B, W.cl, W.cnt, gsrc);
+        uint32_t* bnd2 = (uint32_t*)B.keys_a;  // 2 * cnt u32 fit the keys area
+        uint32_t* hv = bnd2 + cnt;
+        uint32_t* hvs = B.cl1 == W.cl ? B.cl0 : B.cl1;
+        hipLaunchKernelGGL(text_bounds, dim3(grid), dim3(256), 0, st, B, W.cl, W.cnt, gsrc, bnd2);
+        hipLaunchKernelGGL(text_head_slots, dim3(grid), dim3(256), 0, st, W.cl, W.cnt, bnd2, hv);
+        e = rocprim::inclusive_scan(W.tmp, W.tmp_bytes, hv, hvs, (size_t)cnt, rocprim::maximum<uint32_t>(), st);
+        hipLaunchKernelGGL(bwt_rank_all, dim3(8192), dim3(256), 0, st, B, W.N);
+        hipLaunchKernelGGL(text_rank_tied, dim3(grid), dim3(256), 0, st, B, W.cl, W.cnt, hvs);
+        W.cl_next = hvs;
+    }
+    return e;
+}
+
+// Doubling rounds over what the text rounds left (long repeats only), each
+// after a read of the list's length, until nothing is tied or h covers the
+// block (what is still tied then are the equal rotations of a periodic block).
+hipError_t doubling_rounds(const Batch& B, TieRounds& W)
+{
+    hipStream_t st = W.st;
+    uint32_t h = W.covered;
+    const uint32_t max_n = B.cap;
+    while (!W.none_left) {
+        uint32_t cnt = 0;
+        hipError_t e = W.read_count(&cnt);
+        if (e != hipSuccess) return e;
+        if (cnt == 0) break;
+        if (h >= max_n) {  // every remaining tie is a pair of equal rotations
+            hipLaunchKernelGGL(bwt_flag_periodic, dim3(256), dim3(256), 0, st, B, W.cl, W.cnt);
+            break;
+        }
+        const uint32_t grid = list_grid(cnt);
+        hipLaunchKernelGGL(bwt_comp_keys, dim3(grid), dim3(256), 0, st, B, W.cl, W.cnt, h);
+        e = rocprim::radix_sort_pairs(W.tmp, W.tmp_bytes, B.keys_a, B.keys_b, B.vals_a, B.vals_b, cnt, 0, 52, st);
+        if (e != hipSuccess) return e;
+        uint32_t* hv = (uint32_t*)B.keys_a;  // the sort has consumed keys_a
+        uint32_t* hvs = hv + cnt;
+        hipLaunchKernelGGL(bwt_comp_heads, dim3(grid), dim3(256), 0, st, B, W.cl, W.cnt, hv);
+        e = rocprim::inclusive_scan(W.tmp, W.tmp_bytes, hv, hvs, (size_t)cnt, rocprim::maximum<uint32_t>(), st);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(bwt_comp_rank, dim3(grid), dim3(256), 0, st, B, W.cnt, hvs);
+        e = rocprim::select(W.tmp, W.tmp_bytes, W.cl, B.uflag, W.cl_next, W.cnt, (size_t)cnt, st);
+        if (e != hipSuccess) return e;
+        std::swap(W.cl, W.cl_next);
+        h *= 2;
+    }
+    return hipSuccess;
+}
+
+// The rotations to sort, sorted: round 0 (bucket pass + chunk sorts by the
+// 8-byte prefix), then the tie rounds.  Ties that would need prefix doubling
+// (long repeats) restart the batch with every rotation sorted (B.it_full:
+// doubling ranks every rotation), which also finds the periodic blocks.
+hipError_t bwt_sort(Batch& B, const Scratch& S, hipStream_t st, BwtStats* stats)
+{
+    TieRounds W{st, (size_t)B.nstreams * B.cap, S.cnt, S.tmp, S.tmp_bytes, B.cl0, B.cl1, kKeyBytes, false, {},
+                (uint64_t*)B.rank};
+    hipError_t e;
+    for (B.it_full = LFM_BWT_FORCE_FULL;; B.it_full = 1) {
+        if ((e = first_round(B, W)) != hipSuccess || (e = text_rounds(B, W)) != hipSuccess) return e;
+        // ties left (long repeats)
+        uint32_t cnt = 0;
+        if (!W.none_left && (e = W.read_count(&cnt)) != hipSuccess) return e;
+        if (cnt == 0) {
+            W.none_left = true;
+            break;
+        }
+        if (!B.it_full) continue;  // doubling needs the rank of every rotation: sort them all
+        if ((e = rank_rebuild(B, W, cnt)) != hipSuccess) return e;
+        break;
+    }
+    if ((e = doubling_rounds(B, W)) != hipSuccess) return e;
+    if (stats) *stats = W.stats;
+    return hipSuccess;
+}
+
 } // namespace
 
-extern "C" size_t lfm_hip_bzip2_workspace_bytes(uint32_t nstreams, uint32_t raw_cap)
+extern "C" size_t lfm_hip_bzip2_workspace_bytes(uint32_t nstreams, uint32_t block_bytes)
 {
-    const uint32_t cap = (uint32_t)align_up((size_t)raw_cap + raw_cap / 4 + 64, 256);
-    const uint32_t out_cap = (uint32_t)align_up((size_t)raw_cap + raw_cap / 50 + 4096, 256);
-    const uint32_t sel_cap = (uint32_t)align_up(cap / kGSize + 8, 64);
-    const size_t N = (size_t)nstreams * cap;
-    size_t b = 0;
-    b += align_up((size_t)nstreams * align_up(raw_cap, 16), 256);   // raw
-    b += align_up(N, 256);                                      // T
-    b += 2 * align_up(N * 8, 256);                              // keys
-    b += 6 * align_up(N * 4, 256);                              // vals_a, sa, rank, vals_b, cl0, cl1
-    b += align_up(N, 256);                                      // uflag
-    b += align_up((size_t)nstreams * (cap + 8) * 2, 256);       // mtfv
-    b += 2 * align_up((size_t)nstreams * sel_cap, 256);         // sel, sel_mtf
-    b += align_up((size_t)nstreams * kMaxGroups * kMaxAlpha, 256);       // len
-    b += 2 * align_up((size_t)nstreams * kMaxGroups * kMaxAlpha * 4, 256);   // code, rfreq
-    b += align_up((size_t)nstreams * out_cap, 256);             // words
-    b += align_up((size_t)nstreams * kMaxAlpha * 4, 256);       // mtf_freq
-    b += align_up((size_t)nstreams * 8 * 4, 256);               // inuse
-    b += align_up((size_t)nstreams * kMaxGroups * 4 + 64, 256);  // wide heap list
-    b += align_up((size_t)nstreams * 512 * 4, 256);             // A / B rotations per first byte
-    b += align_up((size_t)nstreams * 1024 * 4, 256);            // placement tables
-    b += 16 * align_up((size_t)nstreams * 4 + 64, 256);         // small per-stream arrays
-    b += align_up(((size_t)nstreams + 1) * 8 + 32, 256);        // offsets + counters
-    b += align_up(prim_tmp_bytes(nstreams, cap), 256);          // rocPRIM temporary storage
-    return b;
+    Batch B{};
+    Scratch S{};
+    return layout(nullptr, nstreams, block_bytes, B, S);
 }
+
+extern "C" size_t lfm_hip_bzip2_out_cap(uint32_t block_bytes) { return out_cap(block_bytes); }
 
 // Compress streams [first, first + count) of the block grid of `img`
 // (device, image layout) into `payload` (device, contiguous in block order);
@@ -3648,18 +3701,9 @@ extern "C" int lfm_hip_bzip2_blocks(const void* d_img, const uint32_t dims[5], c
 {
     hipStream_t st = (hipStream_t)stream_;
     if (!d_img || !dims || !bs || !bpp || !count || level < 1 || level > 9 || !d_ws || !d_payload) return LFM_HIP_EINVAL;
-    ensure_crc_table();
-    static thread_local int crc_dev = -1;
     int dev = 0;
     (void)hipGetDevice(&dev);
-    if (crc_dev != dev) {
-        if (hipMemcpyToSymbol(HIP_SYMBOL(c_crc_table), host_crc_table, sizeof(host_crc_table)) != hipSuccess ||
-            hipMemcpyToSymbol(HIP_SYMBOL(c_crc4), host_crc4, sizeof(host_crc4)) != hipSuccess ||
-            hipMemcpyToSymbol(HIP_SYMBOL(c_crc_shb), host_crc_shb, sizeof(host_crc_shb)) != hipSuccess ||
-            hipMemcpyToSymbol(HIP_SYMBOL(c_crc_unshift), host_crc_unshift, sizeof(host_crc_unshift)) != hipSuccess)
-            return LFM_HIP_ERUNTIME;
-        crc_dev = dev;
-    }
+    if (!crc_tables_on_device(dev)) return LFM_HIP_ERUNTIME;
     StageEvents& SE = t_stage;
     SE.valid = false;
     const bool timed = SE.ready(dev);
@@ -3677,48 +3721,11 @@ extern "C" int lfm_hip_bzip2_blocks(const void* d_img, const uint32_t dims[5], c
     }
     B.g.bpp = bpp;
     B.first_block = first;
-    B.nstreams = count;
-    B.raw_cap = (uint32_t)align_up(raw_cap, 16);  // stream stride of the raw blocks (16-byte loads)
-    B.cap = (uint32_t)align_up((size_t)raw_cap + raw_cap / 4 + 64, 256);
-    B.out_cap = (uint32_t)align_up((size_t)raw_cap + raw_cap / 50 + 4096, 256);
-    B.sel_cap = (uint32_t)align_up(B.cap / kGSize + 8, 64);
     B.level = level;
     B.nblock_max = 100000u * level - 19u;
-    if (ws_bytes < lfm_hip_bzip2_workspace_bytes(count, raw_cap)) return LFM_HIP_EINVAL;
-    const size_t N = (size_t)count * B.cap;
-    if (N >= (1ull << 32)) return LFM_HIP_EINVAL;
-    uint8_t* p = (uint8_t*)d_ws;
-    auto take = [&](size_t bytes) { uint8_t* r = p; p += align_up(bytes, 256); return r; };
-    B.raw = take((size_t)count * B.raw_cap);
-    B.T = take(N);
-    B.keys_a = (uint64_t*)take(N * 8);
-    B.keys_b = (uint64_t*)take(N * 8);
-    B.vals_a = (uint32_t*)take(N * 4);
-    B.sa = (uint32_t*)take(N * 4);
-    B.rank = (uint32_t*)take(N * 4);
-    B.vals_b = (uint32_t*)take(N * 4);
-    B.cl0 = (uint32_t*)take(N * 4);
-    B.cl1 = (uint32_t*)take(N * 4);
-    B.uflag = take(N);
-    B.mtfv = (uint16_t*)take((size_t)count * (B.cap + 8) * 2);
-    B.sel = take((size_t)count * B.sel_cap);
-    B.sel_mtf = take((size_t)count * B.sel_cap);
-    B.len = take((size_t)count * kMaxGroups * kMaxAlpha);
-    B.code = (uint32_t*)take((size_t)count * kMaxGroups * kMaxAlpha * 4);
-    B.rfreq = (uint32_t*)take((size_t)count * kMaxGroups * kMaxAlpha * 4);
-    B.words = (uint32_t*)take((size_t)count * B.out_cap);
-    B.mtf_freq = (uint32_t*)take((size_t)count * kMaxAlpha * 4);
-    B.inuse = (uint32_t*)take((size_t)count * 8 * 4);
-    B.wide = (uint32_t*)take((size_t)count * kMaxGroups * 4 + 64);
-    B.abcnt = (uint32_t*)take((size_t)count * 512 * 4);
-    B.itab = (uint32_t*)take((size_t)count * 1024 * 4);
-    uint32_t** small[] = {&B.raw_len, &B.n, &B.crc, &B.flags, &B.done, &B.seg_begin, &B.seg_end, &B.nmtf,
-                          &B.orig_ptr, &B.nsel, &B.ngroups, &B.out_bytes, &B.nsub, &B.bwt_mode};
-    for (uint32_t** q : small) *q = (uint32_t*)take((size_t)count * 4 + 64);
-    for (int k = (int)(sizeof(small) / sizeof(small[0])); k < 16; ++k) (void)take((size_t)count * 4 + 64);
-    uint64_t* offs = (uint64_t*)take(((size_t)count + 1) * 8 + 32);
-    size_t tmp_bytes = prim_tmp_bytes(count, B.cap);
-    void* tmp = take(tmp_bytes);
+    Scratch S{};
+    if (ws_bytes < layout((uint8_t*)d_ws, count, raw_cap, B, S)) return LFM_HIP_EINVAL;
+    if ((size_t)count * B.cap >= (1ull << 32)) return LFM_HIP_EINVAL;
 
     hipError_t e = hipSuccess;
     auto ok = [&]() { return (e = hipGetLastError()) == hipSuccess; };
@@ -3735,193 +3742,11 @@ extern "C" int lfm_hip_bzip2_blocks(const void* d_img, const uint32_t dims[5], c
         hipLaunchKernelGGL(rle1_crc<false>, dim3(count), dim3(kRleThreads), 0, st, B);
     }
     if (!ok()) return LFM_HIP_ERUNTIME;
-    // counters after offs: [0..2] chunk classes 0..2 of the bucket pass (then
-    // the tied-list counts [0], [1]); [3] wide Huffman streams, [4] Huffman
-    // retries, [5] chunk class 3
-    uint32_t* d_cnt = (uint32_t*)(offs + count + 1);
-    B.wide_cnt = d_cnt + 3;
     mark(1);
-    // BWT: the B rotations sorted (round 0 = bucket pass + chunk sorts by the
-    // 8-byte prefix, then the tie rounds), every other rotation placed by
-    // bwt_induce.  Ties that would need prefix doubling (long repeats) restart
-    // the batch with every rotation sorted (B.it_full: doubling ranks every
-    // rotation), which also finds the periodic blocks.
-    uint32_t* cl = B.cl0;
-    uint32_t* cl_next = B.cl1;
-    uint32_t covered = kKeyBytes;
-    bool none_left = false;  // a count read 0 and no kernel ran since: skip the later reads
-    uint32_t first_ties = 0, left_runs = 0;  // tied slots after the chunk sorts, runs tie_runs_direct left (LFM_BZ2_STATS)
-#ifndef LFM_BWT_FORCE_FULL
-#define LFM_BWT_FORCE_FULL 0  // timing variants: every rotation sorted, no induction
-#endif
-#ifndef LFM_BWT_RSORT
-#define LFM_BWT_RSORT 0  // 1: the hand-written radix chunk sort (bwt_chunk_rsort) instead of rocPRIM's merge sort
-#endif
-#if LFM_BWT_RSORT
-#define LFM_CHUNK_SORT bwt_chunk_rsort
-#else
-#define LFM_CHUNK_SORT bwt_chunk_sort
-#endif
-    for (B.it_full = LFM_BWT_FORCE_FULL;; B.it_full = 1) {
-        ChunkLists CL;
-        const size_t q = N / 4;  // chunk lists in the cl0 / cl1 areas (at most 3 n / kChunk + 1 chunks per stream)
-        for (int c = 0; c < 4; ++c) {
-            CL.b[c] = B.cl0 + c * q;
-            CL.e[c] = B.cl1 + c * q;
-        }
-        CL.cnt = d_cnt;
-        CL.cnt3 = d_cnt + 5;
-        uint32_t nch[6] = {0, 0, 0, 0, 0, 0};
-        if (hipMemsetAsync(d_cnt, 0, 32, st) != hipSuccess ||
-            hipMemsetAsync(B.done, 0, (size_t)count * 4, st) != hipSuccess)
-            return LFM_HIP_ERUNTIME;
-        hipLaunchKernelGGL(bwt_bucket<kBucketBits>, dim3(count), dim3(kBucketThreads), 0, st, B, CL);
-        if (!ok() || hipMemcpyAsync(nch, d_cnt, 24, hipMemcpyDeviceToHost, st) != hipSuccess ||
-            hipStreamSynchronize(st) != hipSuccess)
-            return LFM_HIP_ERUNTIME;
-        // chunks in XCD-aware order: workgroup b runs on XCD b % 8
-        auto cs_grid = [&](uint32_t nc, uint32_t& per) {
-            per = (nc + 7) / 8;
-            return dim3(8 * per);
-        };
-        uint32_t per = 0;
-        if (nch[5]) {
-            const dim3 g = cs_grid(nch[5], per);
-            hipLaunchKernelGGL((LFM_CHUNK_SORT<kTinyCap / kCsItems, kCsItems>), g, dim3(kTinyCap / kCsItems), 0, st, B,
-                               CL.b[3], CL.e[3], nch[5], per);
-        }
-        if (nch[0]) {
-            const dim3 g = cs_grid(nch[0], per);
-            hipLaunchKernelGGL((LFM_CHUNK_SORT<kCsThreads, kCsItems>), g, dim3(kCsThreads), 0, st, B, CL.b[0], CL.e[0],
-                               nch[0], per);
-        }
-        if (nch[1]) {
-            const dim3 g = cs_grid(nch[1], per);
-            hipLaunchKernelGGL((LFM_CHUNK_SORT<kBigThreads, kBigItems>), g, dim3(kBigThreads), 0, st, B, CL.b[1],
-                               CL.e[1], nch[1], per);
-        }
-        if (nch[2]) {
-            hipLaunchKernelGGL(bwt_chunk_keys, dim3(nch[2]), dim3(256), 0, st, B, CL.b[2], CL.e[2]);
-            e = rocprim::segmented_radix_sort_pairs(tmp, tmp_bytes, B.keys_a, B.keys_b, B.vals_a, B.sa, (unsigned)N,
-                                                    nch[2], CL.b[2], CL.e[2], 0, 64 - kBucketBits, st);
-            if (e == hipSuccess)
-                hipLaunchKernelGGL(bwt_chunk_flags, dim3(nch[2]), dim3(256), 0, st, B, CL.b[2], CL.e[2]);
-        }
-        if (!ok()) return LFM_HIP_ERUNTIME;
-        cl = B.cl0;
-        cl_next = B.cl1;
-        hipLaunchKernelGGL(tie_offsets, dim3(1), dim3(1024), 0, st, B, d_cnt);
-        hipLaunchKernelGGL(tie_compact, dim3(count), dim3(256), 0, st, B, B.cl0);
-        hipLaunchKernelGGL(tie_runs_direct, dim3(1024), dim3(256), 0, st, B, B.cl0, d_cnt, d_cnt + 7);
-        if (!ok()) return LFM_HIP_ERUNTIME;
-        covered = kKeyBytes;
-        none_left = false;
-        // text rounds over the tied list (group keys: u64 per entry in the rank
-        // area, group index / bounds in the mtfv area -- both free here)
-        uint64_t* gk = (uint64_t*)B.rank;
-        uint32_t* bnd = (uint32_t*)B.mtfv;
-        for (int r = 0; r < kTextRounds && e == hipSuccess; ++r) {
-            // counters: [0] tied slots, [7] runs tie_runs_direct left (read with the first round's count)
-            uint32_t c8[8] = {};
-            if (hipMemcpyAsync(c8, d_cnt, r == 0 ? 32 : 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
-                hipStreamSynchronize(st) != hipSuccess) {
-                e = hipErrorUnknown;
-                break;
-            }
-            const uint32_t cnt = c8[0];
-            if (r == 0) {
-                first_ties = cnt;
-                left_runs = c8[7];
-            }
-            if (cnt == 0 || (r == 0 && c8[7] == 0)) {  // nothing tied, or tie_runs_direct sorted every run
-                none_left = true;
-                break;
-            }
-            if ((size_t)cnt * 4 > N) break;
-            unsigned gbits = 1;
-            while ((1u << gbits) < cnt) ++gbits;
-            // group index above the text bytes in one 64-bit key: fewer text
-            // bytes when the tied list is longer than 2^24
-            const uint32_t tb = std::min<uint32_t>(kTextBytes, (64 - gbits) / 8);
-            uint32_t* gidx = bnd + cnt;
-            const uint32_t grid = std::min<uint32_t>(4096, (cnt + 255) / 256);
-            if (r == 0) hipLaunchKernelGGL(text_gather_keys, dim3(grid), dim3(256), 0, st, B, cl, d_cnt, gk);
-            hipLaunchKernelGGL(text_bounds, dim3(grid), dim3(256), 0, st, B, cl, d_cnt, gk, bnd);
-            e = rocprim::inclusive_scan(tmp, tmp_bytes, bnd, gidx, (size_t)cnt, rocprim::plus<uint32_t>(), st);
-            if (e != hipSuccess) break;
-            hipLaunchKernelGGL(text_keys, dim3(grid), dim3(256), 0, st, B, cl, d_cnt, gidx, covered, tb);
-            e = rocprim::radix_sort_pairs(tmp, tmp_bytes, B.keys_a, B.keys_b, B.vals_a, B.vals_b, cnt, 0,
-                                          8 * tb + gbits, st);
-            if (e != hipSuccess) break;
-            hipLaunchKernelGGL(text_write, dim3(grid), dim3(256), 0, st, B, cl, d_cnt);
-            covered += tb;
-            e = rocprim::select(tmp, tmp_bytes, B.keys_b, B.uflag, gk, d_cnt + 1, (size_t)cnt, st);
-            if (e == hipSuccess) e = rocprim::select(tmp, tmp_bytes, cl, B.uflag, cl_next, d_cnt, (size_t)cnt, st);
-            std::swap(cl, cl_next);
-        }
-        if (e != hipSuccess) return LFM_HIP_ERUNTIME;
-        // ties left (long repeats)
-        uint32_t cnt = 0;
-        if (!none_left && (hipMemcpyAsync(&cnt, d_cnt, 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
-                           hipStreamSynchronize(st) != hipSuccess))
-            return LFM_HIP_ERUNTIME;
-        if (cnt == 0) {
-            none_left = true;
-            break;
-        }
-        if (!B.it_full) continue;  // doubling needs the rank of every rotation: sort them all
-        // ranks of every rotation for doubling: group bounds of the remaining
-        // list from the last text keys, or from the first-round keys when no
-        // text round ran
-        uint64_t* gsrc = gk;
-        const uint32_t grid = std::min<uint32_t>(4096, (cnt + 255) / 256);
-        if (covered == kKeyBytes) gsrc = (uint64_t*)B.vals_b;  // cnt * 8 <= N * 4 when cnt <= N / 2: rank0 otherwise
-        if (covered == kKeyBytes && (size_t)cnt * 2 > N) {
-            hipLaunchKernelGGL(bwt_rank0, dim3(count), dim3(1024), 0, st, B);
-        } else {
-            if (covered == kKeyBytes) hipLaunchKernelGGL(text_gather_keys, dim3(grid), dim3(256), 0, st, B, cl, d_cnt, gsrc);
-            uint32_t* bnd2 = (uint32_t*)B.keys_a;  // 2 * cnt u32 fit the keys area
-            uint32_t* hv = bnd2 + cnt;
-            uint32_t* hvs = (uint32_t*)B.cl1 == cl ? (uint32_t*)B.cl0 : (uint32_t*)B.cl1;
-            hipLaunchKernelGGL(text_bounds, dim3(grid), dim3(256), 0, st, B, cl, d_cnt, gsrc, bnd2);
-            hipLaunchKernelGGL(text_head_slots, dim3(grid), dim3(256), 0, st, cl, d_cnt, bnd2, hv);
-            e = rocprim::inclusive_scan(tmp, tmp_bytes, hv, hvs, (size_t)cnt, rocprim::maximum<uint32_t>(), st);
-            hipLaunchKernelGGL(bwt_rank_all, dim3(8192), dim3(256), 0, st, B, N);
-            hipLaunchKernelGGL(text_rank_tied, dim3(grid), dim3(256), 0, st, B, cl, d_cnt, hvs);
-            cl_next = hvs == (uint32_t*)B.cl0 ? B.cl0 : B.cl1;
-        }
-        break;
-    }
-    // doubling rounds over what the text rounds left (long repeats only, B.it_full)
-    uint32_t h = covered;
-    const uint32_t max_n = B.cap;
-    while (e == hipSuccess && !none_left) {
-        uint32_t cnt = 0;
-        if (hipMemcpyAsync(&cnt, d_cnt, 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
-            hipStreamSynchronize(st) != hipSuccess) {
-            e = hipErrorUnknown;
-            break;
-        }
-        if (cnt == 0) break;
-        if (h >= max_n) {  // every remaining tie is a pair of equal rotations
-            hipLaunchKernelGGL(bwt_flag_periodic, dim3(256), dim3(256), 0, st, B, cl, d_cnt);
-            break;
-        }
-        const uint32_t grid = std::min<uint32_t>(4096, (cnt + 255) / 256);
-        hipLaunchKernelGGL(bwt_comp_keys, dim3(grid), dim3(256), 0, st, B, cl, d_cnt, h);
-        e = rocprim::radix_sort_pairs(tmp, tmp_bytes, B.keys_a, B.keys_b, B.vals_a, B.vals_b, cnt, 0, 52, st);
-        if (e != hipSuccess) break;
-        uint32_t* hv = (uint32_t*)B.keys_a;  // the sort has consumed keys_a
-        uint32_t* hvs = hv + cnt;
-        hipLaunchKernelGGL(bwt_comp_heads, dim3(grid), dim3(256), 0, st, B, cl, d_cnt, hv);
-        e = rocprim::inclusive_scan(tmp, tmp_bytes, hv, hvs, (size_t)cnt, rocprim::maximum<uint32_t>(), st);
-        if (e != hipSuccess) break;
-        hipLaunchKernelGGL(bwt_comp_rank, dim3(grid), dim3(256), 0, st, B, d_cnt, hvs);
-        e = rocprim::select(tmp, tmp_bytes, cl, B.uflag, cl_next, d_cnt, (size_t)cnt, st);
-        std::swap(cl, cl_next);
-        h *= 2;
-    }
-    if (e != hipSuccess) return LFM_HIP_ERUNTIME;
+    // BWT: the rotations of one type sorted (bwt_sort), every other rotation
+    // placed by bwt_induce unless bwt_sort had to sort them all (B.it_full)
+    BwtStats bwt_stats;
+    if (bwt_sort(B, S, st, &bwt_stats) != hipSuccess) return LFM_HIP_ERUNTIME;
     if (!B.it_full) {
         // the other type placed by one scan; the final order in the vals_b area
         B.sfin = B.vals_b;
@@ -3933,7 +3758,7 @@ extern "C" int lfm_hip_bzip2_blocks(const void* d_img, const uint32_t dims[5], c
         B.sa = B.sfin;
     }
     mark(2);
-    if (t_hook) t_hook(t_hook_ctx, 1);  // the doubling / tie rounds above end with a host synchronisation
+    if (t_hook) t_hook(t_hook_ctx, 1);  // the tie rounds of bwt_sort end with a host synchronisation
     {
         const uint32_t nseg_max = (B.cap + kSeg - 1) / kSeg;
         int32_t* seg_last = (int32_t*)B.keys_a;  // free after the BWT (count * nseg_max KiB << N * 8 bytes)
@@ -3977,10 +3802,7 @@ extern "C" int lfm_hip_bzip2_blocks(const void* d_img, const uint32_t dims[5], c
         hipLaunchKernelGGL(huff_select_reg, dim3(count), dim3(kHuffThreads), 0, st, B);
         // uniform heaps, 32 per workgroup: u32 entries for the narrow tables,
         // u64 for the streams rle2 listed, in one launch
-#ifndef LFM_HUFF_PLANE
-#define LFM_HUFF_PLANE 32
-#endif
-        constexpr uint32_t kPlane = LFM_HUFF_PLANE;  // (stream, table) heaps per wave
+        constexpr uint32_t kPlane = 32;  // (stream, table) heaps per wave
         const uint32_t nn = (count * kMaxGroups + kPlane - 1) / kPlane;
         const uint32_t nw = (nwide * kMaxGroups + kPlane / 2 - 1) / (kPlane / 2);
         hipLaunchKernelGGL(huff_lengths_heap<kPlane>, dim3(nn + nw), dim3(64), 0, st, B, nw, nwide);
@@ -3989,18 +3811,18 @@ extern "C" int lfm_hip_bzip2_blocks(const void* d_img, const uint32_t dims[5], c
     mark(4);
     const bool hook3 = t_hook && ev_tables && hipEventRecord(ev_tables, st) == hipSuccess;
     hipLaunchKernelGGL(emit_stream, dim3(count), dim3(kEmitThreads), 0, st, B);
-    hipLaunchKernelGGL(scan_offsets, dim3(1), dim3(1024), 0, st, B.out_bytes, count, offs);
-    hipLaunchKernelGGL(compact_streams, dim3(count), dim3(256), 0, st, B, offs, (uint8_t*)d_payload);
+    hipLaunchKernelGGL(scan_offsets, dim3(1), dim3(1024), 0, st, B.out_bytes, count, S.offs);
+    hipLaunchKernelGGL(compact_streams, dim3(count), dim3(256), 0, st, B, S.offs, (uint8_t*)d_payload);
     mark(5);
     if (!ok()) return LFM_HIP_ERUNTIME;
     if (hook3 && hipEventSynchronize(ev_tables) == hipSuccess) t_hook(t_hook_ctx, 3);
     static const bool stats = std::getenv("LFM_BZ2_STATS") && std::atoi(std::getenv("LFM_BZ2_STATS")) != 0;
     if (stats) {
         uint32_t c[8] = {};
-        if (hipMemcpyAsync(c, d_cnt, 32, hipMemcpyDeviceToHost, st) == hipSuccess && hipStreamSynchronize(st) == hipSuccess)
+        if (hipMemcpyAsync(c, S.cnt, 32, hipMemcpyDeviceToHost, st) == hipSuccess && hipStreamSynchronize(st) == hipSuccess)
             std::fprintf(stderr, "lfm_bzip2 stats: %u streams, %u with u64 Huffman heaps, Huffman retries %u, "
-                         "tied after the chunk sorts %u, runs left to the tie rounds %u\n", count, c[3], c[4], first_ties,
-                         left_runs);
+                         "tied after the chunk sorts %u, runs left to the tie rounds %u\n", count, c[3], c[4],
+                         bwt_stats.first_ties, bwt_stats.left_runs);
     }
     std::vector<uint32_t> nbytes(count);
     if (hipMemcpyAsync(nbytes.data(), B.out_bytes, count * 4, hipMemcpyDeviceToHost, st) != hipSuccess ||

@@ -717,8 +717,7 @@ int Encoder::gpu_compress(const uint8_t* d_sym, klb_image_header& h, Sink& sink,
     const size_t bpp = h.getBytesPerPixel();
     const uint32_t block_bytes = h.getBlockSizeBytes();
     if (level < 1) level = bzip2_level(h);
-    const size_t out_cap = ((size_t)block_bytes + block_bytes / 50 + 4096 + 255) / 256 * 256;
-    const size_t rle_cap = ((size_t)block_bytes + block_bytes / 4 + 64 + 255) / 256 * 256;
+    const size_t out_cap = bz::out_cap(block_bytes), rle_cap = bz::rle_cap(block_bytes);
     // Batches run in a pipeline of kBzSlots HIP streams (one host thread
     // each): one batch's latency-bound stages (MTF, Huffman tables, the
     // host-synchronised doubling rounds) overlap another batch's sorts.  The

@@ -9,6 +9,7 @@
 #include <cstdlib>
 #include <thread>
 #include <vector>
+#include "lfm_bz_caps.h"  // per-stream capacities of the GPU bzip2 encoder (bz::out_cap, bz::rle_cap)
 
 #pragma GCC visibility push(hidden)
 namespace lfm {

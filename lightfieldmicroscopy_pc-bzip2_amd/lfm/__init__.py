@@ -41,7 +41,7 @@ EXPORTS = [
     # lfm_hip.h
     "lfm_hip_predict", "lfm_hip_unpredict", "lfm_hip_unpredict_async", "lfm_hip_unpredict_check",
     "lfm_hip_predict_candidates", "lfm_hip_entropy2d", "lfm_hip_select_workspace_bytes", "lfm_hip_select",
-    "lfm_hip_synth", "lfm_hip_device_count", "lfm_hip_force_generic", "lfm_hip_bzip2_workspace_bytes",
+    "lfm_hip_synth", "lfm_hip_device_count", "lfm_hip_force_generic", "lfm_hip_bzip2_workspace_bytes", "lfm_hip_bzip2_out_cap",
     "lfm_hip_bzip2_blocks", "lfm_hip_bzip2_last_stage_ms", "lfm_hip_bunzip2_workspace_bytes", "lfm_hip_bunzip2_blocks", "lfm_hip_scatter_blocks",
     "lfm_hip_crop_region",
 ]
@@ -149,6 +149,8 @@ def lib():
     L.lfm_hip_entropy2d.argtypes = [vp, ctypes.c_uint64, f32p, vp]
     L.lfm_hip_bzip2_workspace_bytes.argtypes = [ctypes.c_uint32, ctypes.c_uint32]
     L.lfm_hip_bzip2_workspace_bytes.restype = ctypes.c_size_t
+    L.lfm_hip_bzip2_out_cap.argtypes = [ctypes.c_uint32]
+    L.lfm_hip_bzip2_out_cap.restype = ctypes.c_size_t
     L.lfm_hip_bzip2_blocks.argtypes = [vp, u32p, u32p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
                                        ctypes.c_uint32, vp, ctypes.c_size_t, vp,
                                        ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint32), vp]
@@ -719,7 +721,7 @@ def bzip2_device(d_img, dims, block, bpp, level=None, first=0, count=None, strea
     level = min(9, -(-block_bytes // 100000)) if level is None else level
     ws_bytes = lib().lfm_hip_bzip2_workspace_bytes(count, block_bytes)
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=d_img.device)
-    out_cap = ((block_bytes + block_bytes // 50 + 4096 + 255) // 256) * 256
+    out_cap = lib().lfm_hip_bzip2_out_cap(block_bytes)
     pay = torch.empty(count * out_cap, dtype=torch.uint8, device=d_img.device)
     sizes = (ctypes.c_uint64 * count)()
     flags = (ctypes.c_uint32 * count)()

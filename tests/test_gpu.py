@@ -492,6 +492,59 @@ def test_gpu_bzip2_block_grid_and_symbols(lfmlib, oracle, gpu):
         assert g == ref_bz2(oracle, raw, 1), i
 
 
+@pytest.mark.parametrize("dims,bs,dtype", [
+    ([4096, 1, 3, 1, 1], [4096, 1, 1, 1, 1], np.uint8),   # 3 streams of 4 096 bytes: RLE1 reads the image
+    ([40, 6, 2, 1, 1], [24, 4, 1, 1, 1], np.uint16),      # border blocks, rows of 48 / 32 bytes
+    ([42, 6, 2, 1, 1], [24, 4, 1, 1, 1], np.uint16),      # image rows of 84 bytes: gather_blocks runs first
+], ids=["direct", "grid40", "grid42-gather"])
+def test_gpu_bzip2_workspace_is_exactly_its_size(lfmlib, oracle, gpu, dims, bs, dtype):
+    """lfm_hip_bzip2_blocks through ctypes with a workspace of exactly
+    lfm_hip_bzip2_workspace_bytes(count, block_bytes), 256-byte aligned, between
+    two 4 KiB guard regions: the guards stay untouched, the streams are the
+    reference library's bytes, and one byte less is refused before anything
+    runs.  (The size and the carving come from one buffer list; this is what
+    fails when they disagree.)"""
+    torch = gpu
+    import ctypes
+    L = lfmlib.lib()
+    GUARD, FILL = 4096, 0xA5
+    LFM_HIP_OK, LFM_HIP_EINVAL = 0, 1  # lfm_hip.h
+    bpp = np.dtype(dtype).itemsize
+    rng = np.random.default_rng(5)
+    img = rng.integers(0, 7, dims[::-1], dtype=np.uint8).astype(dtype)  # t c z y x; low entropy, not periodic
+    d = torch.from_numpy(img.view(np.int16 if bpp == 2 else np.uint8).copy()).cuda()
+    blocks = list(oracle.iter_blocks(dims, bs))
+    count, block_bytes = len(blocks), int(np.prod(bs)) * bpp
+    ws_bytes = L.lfm_hip_bzip2_workspace_bytes(count, block_bytes)
+    out_cap = L.lfm_hip_bzip2_out_cap(block_bytes)
+    buf = torch.full((GUARD + 256 + ws_bytes + GUARD,), FILL, dtype=torch.uint8, device="cuda")
+    lo = GUARD + (-(buf.data_ptr() + GUARD)) % 256   # workspace base: 256-byte aligned, a guard before it
+    assert (buf.data_ptr() + lo) % 256 == 0
+    pay = torch.full((count * out_cap,), 0x5A, dtype=torch.uint8, device="cuda")
+    torch.cuda.synchronize()
+
+    def call(nbytes):
+        sizes, flags = (ctypes.c_uint64 * count)(), (ctypes.c_uint32 * count)()
+        rc = L.lfm_hip_bzip2_blocks(d.data_ptr(), (ctypes.c_uint32 * 5)(*dims), (ctypes.c_uint32 * 5)(*bs), bpp, 0,
+                                    count, 1, buf.data_ptr() + lo, nbytes, pay.data_ptr(), sizes, flags, None)
+        torch.cuda.synchronize()
+        return rc, list(sizes), list(flags)
+
+    rc, sizes, flags = call(ws_bytes - 1)
+    assert rc == LFM_HIP_EINVAL
+    assert not any(sizes) and bool((buf == FILL).all()) and bool((pay == 0x5A).all())  # nothing ran
+    rc, sizes, flags = call(ws_bytes)
+    assert rc == LFM_HIP_OK and not any(flags)
+    assert bool((buf[:lo] == FILL).all()), "guard before the workspace written"
+    assert bool((buf[lo + ws_bytes:] == FILL).all()), "guard after the workspace written"
+    host = pay[:sum(sizes)].cpu().numpy().tobytes()
+    o = 0
+    for (i, coord, size), n in zip(blocks, sizes):
+        raw = oracle.gather_block(img, coord, size)
+        assert host[o:o + n] == ref_bz2(oracle, raw, 1), i
+        o += n
+
+
 def test_gpu_bzip2_many_wide_heaps(lfmlib, oracle, gpu):
     """200 random 160 kB streams: 1 200 Huffman tables whose weights leave the
     packed heap's 17 bits, more than one pass of the wide-heap kernel's grid;
