@@ -220,6 +220,77 @@ LFM_API int lfm_decode_memory_roi_device(const uint8_t* buf, uint64_t len, const
                                          const uint32_t ub[KLB_DATA_DIMS], void* d_out, uint64_t out_bytes,
                                          int numThreads, lfm_decode_stats* stats);
 
+/* Devices the whole-image readers farm block-layer ranges to, one host
+ * thread per entry (a device may repeat: several workers on one GPU).  The
+ * list is opt-in: n > 0 sets it, n = 0 restores the default, which is env
+ * LFM_DECODE_GPUS = "0,1,.." or a count (the syntax of LFM_GPUS) and empty
+ * without it.  With fewer than two entries every reader runs on the current
+ * device exactly as before.  With two or more, lfm_decode_memory,
+ * readLFMstack_c, readKLBstack, readKLBstackInPlace and
+ * klb_imageIO::readImageFull decode as lfm_decode_memory_multi does; region
+ * reads are never farmed.  lfm_get_decode_devices returns the count and fills
+ * up to cap entries. */
+LFM_API int lfm_set_decode_devices(const int* devices, int n);
+LFM_API int lfm_get_decode_devices(int* devices, int cap);
+/* The env parse alone, for n_visible devices (no device call). */
+LFM_API int lfm_default_decode_devices(int n_visible, int* devices, int cap);
+/* End the readers' kept worker threads: the device and pinned buffers they
+ * hold between calls are freed (the next farmed decode starts them again).
+ * lfm_release_encoders is about the writers only. */
+LFM_API void lfm_release_decoders(void);
+
+/* One shard of a farmed decode: indices [first, first + count) along the
+ * shard axis, decoded on `device` with status rc. */
+typedef struct lfm_decode_shard {
+    uint32_t first, count;   /* along the axis */
+    int device;              /* -1: no device (a host decode on a GPU-less machine) */
+    int rc;
+    lfm_decode_stats stats;  /* this shard's */
+} lfm_decode_shard;
+
+typedef struct lfm_decode_multi_stats {
+    double total_ms;
+    int axis;                /* 2 / 3 / 4: the shards are ranges of z / c / t */
+    int workers;             /* shards decoded side by side; 1 = not farmed */
+    uint64_t blocks, host_blocks, d2h_bytes;   /* summed over the shards */
+} lfm_decode_multi_stats;
+
+/* How a file is cut for nworkers readers: the writers' split.  The axis is t
+ * when xyzct[4] > 1, else c when xyzct[3] > 1, else z; a shard is a range of
+ * whole block layers along it (on the z axis of a predicted video file with an
+ * odd block depth, of pairs of layers, so every shard starts at an even z):
+ * per = ceil(layers / nworkers) layers each, ceil(layers / per) shards.
+ * Fills *axis and up to cap entries of first / count (each may be NULL) and
+ * returns the shard count (>= 1; asking for that many workers gives the same
+ * shards again), or 0 on a bad header. */
+LFM_API int lfm_decode_shard_plan(const uint8_t* buf, uint64_t len, int nworkers, int* axis, uint32_t* first,
+                                  uint32_t* count, int cap);
+
+/* lfm_decode_memory with one worker per entry of the decode device list:
+ * shard w of lfm_decode_shard_plan(.., list length, ..) is decoded by its own
+ * host thread (numThreads / shards host threads each, at least 1) on device
+ * list[w], straight into its slice of img; no data crosses between devices and
+ * no block is decoded twice.  One plain decode on the current device instead
+ * (stats->workers = 1) when the list has fewer than two entries, the file is
+ * one shard, or the pipelined GPU decode does not take it (compression NONE /
+ * ZLIB, Nnum > 31, non-contiguous block offsets, LFM_GPU_DECODE=0 or
+ * LFM_GPU_BUNZIP2=0, no GPU).  Returns the first non-zero shard status in
+ * shard order, after every worker has finished.  The workers keep their
+ * device buffers between calls (lfm_release_decoders).  stats and shards may
+ * be NULL; up to shard_cap shards are filled. */
+LFM_API int lfm_decode_memory_multi(const uint8_t* buf, uint64_t len, void* img, int numThreads,
+                                    lfm_decode_multi_stats* stats, lfm_decode_shard* shards, int shard_cap);
+
+/* The same into DEVICE memory, one buffer per shard: d_out[w] (out_bytes[w]
+ * bytes) takes shard w of lfm_decode_shard_plan(.., nshards, ..), x fastest.
+ * nshards must be the count that plan returns for nshards workers; anything
+ * else returns 3.  Each shard runs on its buffer's device, found as
+ * lfm_decode_memory_device finds it (the decode device list is not used), and
+ * that function's ordering and failure rules hold per buffer. */
+LFM_API int lfm_decode_memory_multi_device(const uint8_t* buf, uint64_t len, void* const* d_out,
+                                           const uint64_t* out_bytes, int nshards, int numThreads,
+                                           lfm_decode_multi_stats* stats, lfm_decode_shard* shards, int shard_cap);
+
 #ifdef __cplusplus
 }
 #endif

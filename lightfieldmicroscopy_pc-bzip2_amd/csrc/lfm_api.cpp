@@ -245,12 +245,72 @@ extern "C" int lfm_decode_memory(const uint8_t* buf, uint64_t len, void* img, in
     klb_image_header h;
     int rc = h.parseHeader(buf, len);
     if (rc) return rc;
-    const size_t hs = h.getSizeInBytes();
-    rc = lfm::decode_payload(buf + hs, len - hs, h, (uint8_t*)img, numThreads, lfm::current_family());
+    rc = lfm::decode_image(buf, len, h, (uint8_t*)img, numThreads);
     if (std::getenv("LFM_DECODE_TIMING"))
         std::fprintf(stderr, "decode total (C)     %8.2f ms\n",
                      std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
     return rc;
+}
+
+extern "C" int lfm_set_decode_devices(const int* devices, int n)
+{
+    if (n < 0 || (n > 0 && !devices)) return 3;
+    std::vector<int> d(devices, devices + n);
+    const int count = n > 0 ? lfm_hip_device_count() : 0;
+    for (int v : d)
+        if (v < 0 || v >= count) return 3;
+    lfm::set_decode_devices(d);
+    return 0;
+}
+
+extern "C" int lfm_get_decode_devices(int* devices, int cap)
+{
+    const std::vector<int> d = lfm::decode_devices();
+    for (int i = 0; devices && i < cap && i < (int)d.size(); ++i) devices[i] = d[i];
+    return (int)d.size();
+}
+
+extern "C" int lfm_default_decode_devices(int n_visible, int* devices, int cap)
+{
+    const std::vector<int> d = lfm::default_decode_devices(n_visible);
+    for (int i = 0; devices && i < cap && i < (int)d.size(); ++i) devices[i] = d[i];
+    return (int)d.size();
+}
+
+extern "C" void lfm_release_decoders(void) { lfm::release_decode_workers(); }
+
+extern "C" int lfm_decode_shard_plan(const uint8_t* buf, uint64_t len, int nworkers, int* axis, uint32_t* first,
+                                     uint32_t* count, int cap)
+{
+    klb_image_header h;
+    if (!buf || h.parseHeader(buf, len)) return 0;
+    const lfm::ShardPlan p = lfm::decode_shard_plan(h, nworkers);
+    if (axis) *axis = p.axis;
+    for (int w = 0; w < cap && w < (int)p.shards.size(); ++w) {
+        if (first) first[w] = p.shards[w].first;
+        if (count) count[w] = p.shards[w].second;
+    }
+    return (int)p.shards.size();
+}
+
+extern "C" int lfm_decode_memory_multi(const uint8_t* buf, uint64_t len, void* img, int numThreads,
+                                       lfm_decode_multi_stats* stats, lfm_decode_shard* shards, int shard_cap)
+{
+    if (!buf || !img) return 3;
+    klb_image_header h;
+    if (int rc = h.parseHeader(buf, len)) return rc;
+    return lfm::decode_multi(buf, len, h, (uint8_t*)img, nullptr, nullptr, 0, numThreads, lfm::decode_devices(), stats,
+                             shards, shard_cap);
+}
+
+extern "C" int lfm_decode_memory_multi_device(const uint8_t* buf, uint64_t len, void* const* d_out,
+                                              const uint64_t* out_bytes, int nshards, int numThreads,
+                                              lfm_decode_multi_stats* stats, lfm_decode_shard* shards, int shard_cap)
+{
+    if (!buf || !d_out || !out_bytes || nshards < 1 || lfm_hip_device_count() <= 0) return 3;
+    klb_image_header h;
+    if (int rc = h.parseHeader(buf, len)) return rc;
+    return lfm::decode_multi(buf, len, h, nullptr, d_out, out_bytes, nshards, numThreads, {}, stats, shards, shard_cap);
 }
 
 extern "C" int lfm_decode_memory_device(const uint8_t* buf, uint64_t len, void* d_img, uint64_t d_img_bytes,

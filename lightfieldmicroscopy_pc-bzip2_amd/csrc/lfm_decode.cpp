@@ -531,8 +531,10 @@ bool decode_job_buffers(DecodeJob& J, size_t pay_bytes, size_t img_bytes, uint32
 // downloader thread only waits for each chunk's event and checks its status
 // words, and every slot stream waits for dd->after_caller before the chunk's
 // first kernel that writes img.
+// stats (optional): chunks, blocks and host_blocks are set and the image
+// bytes copied down are added to d2h_bytes.
 static int gpu_decode(const uint8_t* payload, size_t len, const klb_image_header& h, uint8_t* img, int family,
-                      bool predicted, int k, int video, int threads, DeviceDest* dd = nullptr)
+                      bool predicted, int k, int video, int threads, DeviceDest* dd, lfm_decode_stats* stats)
 {
     const BlockGrid g(h);
     const uint64_t nb = g.nblocks;
@@ -651,17 +653,18 @@ static int gpu_decode(const uint8_t* payload, size_t len, const klb_image_header
                      (unsigned long long)nch, (unsigned long long)P.batch, ms_between(tl.t_start, t_alloc), t_up,
                      J.t_wait, J.t_host, J.t_down, ms_since(tl.t_start));
     }
-    if (dd) {
-        dd->stats.chunks = (uint32_t)nch;
-        dd->stats.blocks = nb;
-        dd->stats.host_blocks = J.host_blocks;
+    if (stats) {
+        stats->chunks = (uint32_t)nch;
+        stats->blocks = nb;
+        stats->host_blocks = J.host_blocks;
+        stats->d2h_bytes += J.d2h_bytes;
     }
     release_unless_kept(DB);
     return rc;
 }
 
 int decode_payload(const uint8_t* payload, size_t len, const klb_image_header& h, uint8_t* img, int threads,
-                   int family, DeviceDest* dd)
+                   int family, DeviceDest* dd, lfm_decode_stats* hstats)
 {
     if (threads <= 0) threads = default_threads();
     const BlockGrid g(h);
@@ -681,7 +684,7 @@ int decode_payload(const uint8_t* payload, size_t len, const klb_image_header& h
         // one copy uploads, on the null stream and so behind the caller's work
         if (h.compressionType == BZIP2 && gpu_decode_enabled() && gpu_bunzip2_enabled() &&
             (!predicted || h.Nnum <= 31)) {
-            const int rc = gpu_decode(payload, len, h, img, family, predicted, k, video, threads, dd);
+            const int rc = gpu_decode(payload, len, h, img, family, predicted, k, video, threads, dd, &dd->stats);
             if (rc != -1) {
                 dd->stats.path = 0;
                 return rc;
@@ -702,9 +705,26 @@ int decode_payload(const uint8_t* payload, size_t len, const klb_image_header& h
     }
     if (h.compressionType == BZIP2 && gpu_decode_enabled() && gpu_bunzip2_enabled() && lfm_hip_device_count() > 0 &&
         (!predicted || h.Nnum <= 31)) {
-        const int rc = gpu_decode(payload, len, h, img, family, predicted, k, video, threads);
-        if (rc != -1) return rc;
+        const int rc = gpu_decode(payload, len, h, img, family, predicted, k, video, threads, nullptr, hstats);
+        if (rc != -1) {
+            if (hstats) hstats->path = 0;
+            return rc;
+        }
     }
+    // what the host reader below does, for a caller that asked (its image
+    // bytes that come down are the GPU inverse predictor's)
+    struct HostStats {
+        lfm_decode_stats* s;
+        uint64_t nb, down0;
+        ~HostStats()
+        {
+            if (!s) return;
+            s->path = 1;
+            s->chunks = 0;
+            s->blocks = s->host_blocks = nb;
+            s->d2h_bytes += tl_d2h_bytes - down0;
+        }
+    } host_stats{hstats, g.nblocks, tl_d2h_bytes};
     std::vector<uint16_t> symbuf;
     uint8_t* sym = img;
     if (predicted) {
@@ -800,7 +820,7 @@ int decode_payload(const uint8_t* payload, size_t len, const klb_image_header& h
 // as if they were the whole frame, which is wrong with predictors
 // (klb_imageIO.cpp:2614-2682).
 int decode_roi(const uint8_t* payload, size_t len, const klb_image_header& h, const uint32_t lb[5],
-               const uint32_t ub[5], uint8_t* out, int threads, int family, DeviceDest* dd)
+               const uint32_t ub[5], uint8_t* out, int threads, int family, DeviceDest* dd, lfm_decode_stats* hstats)
 {
     const BlockGrid g(h);
     if (g.nblocks != h.Nb) return 3;
@@ -865,7 +885,7 @@ int decode_roi(const uint8_t* payload, size_t len, const klb_image_header& h, co
     // decoded straight into `out`: no temporary image, no crop
     bool exact = true;
     for (int d = 0; d < 5; ++d) exact = exact && o[d] == lb[d] && n[d] == (uint64_t)ub[d] - lb[d] + 1;
-    if (exact) return decode_payload(spay, total, sub, out, threads, family, dd);
+    if (exact) return decode_payload(spay, total, sub, out, threads, family, dd, hstats);
     if (dd) {
         // the sub-image is decoded into a device buffer kept between calls and
         // the region copied out of it on the device, behind the caller's work
@@ -895,7 +915,7 @@ int decode_roi(const uint8_t* payload, size_t len, const klb_image_header& h, co
         return rc;
     }
     std::unique_ptr<uint8_t[]> simg(new uint8_t[sub.getImageSizeBytes()]);  // (no zero fill: every byte is decoded)
-    const int rc = decode_payload(spay, total, sub, simg.get(), threads, family);
+    const int rc = decode_payload(spay, total, sub, simg.get(), threads, family, nullptr, hstats);
     if (rc) return rc;
     const size_t row = (size_t)(ub[0] - lb[0] + 1) * bpp;
     const uint64_t ny = (uint64_t)ub[1] - lb[1] + 1, nz = (uint64_t)ub[2] - lb[2] + 1, nc = (uint64_t)ub[3] - lb[3] + 1;
@@ -989,8 +1009,7 @@ int decode_file(const char* filename, klb_image_header& h, std::vector<uint8_t>*
         img_out->resize(h.getImageSizeBytes());
         dst = img_out->data();
     }
-    const size_t hs = h.getSizeInBytes();
-    return decode_payload(buf.data() + hs, buf.size() - hs, h, dst, threads, current_family());
+    return decode_image(buf.data(), buf.size(), h, dst, threads);
 }
 
 } // namespace lfm

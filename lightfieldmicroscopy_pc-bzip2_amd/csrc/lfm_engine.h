@@ -304,9 +304,11 @@ struct DeviceDest {
 };
 
 // Decode the payload of a .lfm (bytes after the header) into img (host memory,
-// or device memory when dd is given).
+// or device memory when dd is given).  hstats (optional, host destination):
+// what the decode did, as dd->stats reports it for a device destination
+// (path 1: the host reader); total_ms and staged_bytes are the caller's.
 int decode_payload(const uint8_t* payload, size_t len, const klb_image_header& h, uint8_t* img, int threads,
-                   int family, DeviceDest* dd = nullptr);
+                   int family, DeviceDest* dd = nullptr, lfm_decode_stats* hstats = nullptr);
 int decode_file(const char* filename, klb_image_header& h, std::vector<uint8_t>* img_out, uint8_t* img_into,
                 int threads);
 // ROI read: only the blocks the ROI depends on are decoded (lb / ub inclusive).
@@ -314,7 +316,8 @@ int decode_file(const char* filename, klb_image_header& h, std::vector<uint8_t>*
 // any other decodes its sub-image into a kept device buffer and
 // lfm_hip_crop_region writes `out` (stats.staged_bytes = that sub-image).
 int decode_roi(const uint8_t* payload, size_t len, const klb_image_header& h, const uint32_t lb[5],
-               const uint32_t ub[5], uint8_t* out, int threads, int family, DeviceDest* dd = nullptr);
+               const uint32_t ub[5], uint8_t* out, int threads, int family, DeviceDest* dd = nullptr,
+               lfm_decode_stats* hstats = nullptr);
 // The two device-destination readers behind the C ABI: find the buffer's
 // device (3 for a host or unregistered pointer), run the decode there with the
 // ordering of DeviceDest and restore the caller's current device.
@@ -322,5 +325,46 @@ int decode_memory_device(const uint8_t* buf, uint64_t len, const uint32_t* lb, c
                          uint64_t out_bytes, int threads, lfm_decode_stats* stats);
 int decode_file_roi(const char* filename, klb_image_header& h, const uint32_t lb[5], const uint32_t ub[5],
                     uint8_t* out, int threads);
+
+// ---- multi-GPU reader (lfm_decode_multi.cpp) ----
+// Devices the whole-image readers farm block-layer ranges to.  Opt-in:
+// lfm_set_decode_devices, else env LFM_DECODE_GPUS (the syntax of LFM_GPUS),
+// else empty.  Fewer than two entries: the reader runs on the current device
+// as ever.
+std::vector<int> decode_devices();
+void set_decode_devices(const std::vector<int>& devs);
+// env LFM_DECODE_GPUS for n visible devices (no device call)
+std::vector<int> default_decode_devices(int n);
+// "0,1,2" (a device may repeat) or a count, entries outside [0, n) dropped:
+// the value of LFM_GPUS / LFM_DECODE_GPUS
+std::vector<int> parse_device_list(const char* s, int n);
+
+// How a whole image is cut for `nworkers` readers: the writer's split
+// (encode_multi) along t, else c, else z, in whole block layers; on the z axis
+// of a predicted video file with an odd block depth in pairs of layers, so
+// every shard starts at an even z and decode_roi decodes exactly the shard's
+// blocks.  One shard = the whole axis when the image does not split.
+struct ShardPlan {
+    int axis = 2;
+    std::vector<std::pair<uint32_t, uint32_t>> shards;  // (first, count) along the axis
+};
+ShardPlan decode_shard_plan(const klb_image_header& h, int nworkers);
+
+// Decode the .lfm at buf (header h already parsed from it) with one host
+// thread per shard of decode_shard_plan(h, devs.size()), each on its device
+// with its own kept decode state, into img (host, the whole image) or, when
+// d_out is given, into d_out[w] (device, out_bytes[w] bytes, shard w alone;
+// the plan is then that of n_out workers and each shard runs on its
+// buffer's device).  A file that does not split, or that the pipelined GPU
+// decode does not take, is one plain decode_payload into img.  Returns the
+// first non-zero shard status in shard order.
+int decode_multi(const uint8_t* buf, size_t len, const klb_image_header& h, uint8_t* img, void* const* d_out,
+                 const uint64_t* out_bytes, int n_out, int threads, const std::vector<int>& devs,
+                 lfm_decode_multi_stats* stats, lfm_decode_shard* shards, int shard_cap);
+// The whole-image host readers' decode (lfm_decode_memory, decode_file):
+// decode_multi when decode_devices() names two or more, else decode_payload.
+int decode_image(const uint8_t* buf, size_t len, const klb_image_header& h, uint8_t* img, int threads);
+// stop the kept decode workers; their device and pinned buffers are freed
+void release_decode_workers();
 
 } // namespace lfm

@@ -1,5 +1,5 @@
 // lfm_internal.h -- what the host engine's files (lfm_engine.cpp,
-// lfm_encode.cpp, lfm_decode.cpp, lfm_transfer.cpp) share with each other and
+// lfm_encode.cpp, lfm_decode.cpp, lfm_decode_multi.cpp, lfm_transfer.cpp) share with each other and
 // with nobody else.  Nothing here is exported from liblfm.so.
 #pragma once
 #include <algorithm>

@@ -63,29 +63,37 @@ int env_int(const char* name, int dflt)
 }
 } // namespace
 
+// "0,1,2,3" (a device list; repeats map several workers onto one device) or
+// "N" (devices 0 .. N-1)
+std::vector<int> parse_device_list(const char* e, int n)
+{
+    std::vector<int> out;
+    if (!e || n <= 0) return out;
+    std::string s(e);
+    if (!s.empty() && s.find(',') == std::string::npos) {
+        const int k = std::atoi(s.c_str());
+        for (int i = 0; i < k && i < n; ++i) out.push_back(i);
+    } else {
+        size_t p = 0;
+        while (p < s.size()) {
+            size_t q = s.find(',', p);
+            if (q == std::string::npos) q = s.size();
+            if (q > p) {
+                const int d = std::atoi(s.substr(p, q - p).c_str());
+                if (d >= 0 && d < n) out.push_back(d);
+            }
+            p = q + 1;
+        }
+    }
+    return out;
+}
+
 std::vector<int> default_devices(int n, int current)
 {
     std::vector<int> out;
     if (n <= 0) return out;
-    // LFM_GPUS: "0,1,2,3" (a device list; repeats map several workers onto
-    // one device) or "N" (devices 0 .. N-1)
     if (const char* e = std::getenv("LFM_GPUS")) {
-        std::string s(e);
-        if (!s.empty() && s.find(',') == std::string::npos) {
-            const int k = std::atoi(s.c_str());
-            for (int i = 0; i < k && i < n; ++i) out.push_back(i);
-        } else {
-            size_t p = 0;
-            while (p < s.size()) {
-                size_t q = s.find(',', p);
-                if (q == std::string::npos) q = s.size();
-                if (q > p) {
-                    const int d = std::atoi(s.substr(p, q - p).c_str());
-                    if (d >= 0 && d < n) out.push_back(d);
-                }
-                p = q + 1;
-            }
-        }
+        out = parse_device_list(e, n);
         if (!out.empty()) return out;
     }
     // A process of a multi-process job (torchrun / MPI launchers set these).

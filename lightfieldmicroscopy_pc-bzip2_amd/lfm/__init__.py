@@ -38,6 +38,8 @@ EXPORTS = [
     "lfm_merge_slabs", "lfm_free", "lfm_decode_memory", "lfm_decode_memory_roi", "lfm_set_devices", "lfm_get_devices", "lfm_default_devices",
     "lfm_encoder_encode_multi", "lfm_release_encoders", "lfm_slab_info", "lfm_place_slab", "lfm_encoder_submit",
     "lfm_encoder_submit_select", "lfm_encoder_wait", "lfm_decode_memory_device", "lfm_decode_memory_roi_device",
+    "lfm_set_decode_devices", "lfm_get_decode_devices", "lfm_default_decode_devices", "lfm_release_decoders",
+    "lfm_decode_shard_plan", "lfm_decode_memory_multi", "lfm_decode_memory_multi_device",
     # lfm_hip.h
     "lfm_hip_predict", "lfm_hip_unpredict", "lfm_hip_unpredict_async", "lfm_hip_unpredict_check",
     "lfm_hip_predict_candidates", "lfm_hip_entropy2d", "lfm_hip_select_workspace_bytes", "lfm_hip_select",
@@ -70,6 +72,24 @@ class DecodeStats(ctypes.Structure):
     _fields_ = [("total_ms", ctypes.c_double), ("path", ctypes.c_int), ("chunks", ctypes.c_uint32),
                 ("blocks", ctypes.c_uint64), ("host_blocks", ctypes.c_uint64), ("d2h_bytes", ctypes.c_uint64),
                 ("staged_bytes", ctypes.c_uint64)]
+
+    def as_dict(self):
+        return {f: getattr(self, f) for f, _ in self._fields_}
+
+
+class DecodeShard(ctypes.Structure):
+    """lfm_decode_shard (lfm_api.h)."""
+    _fields_ = [("first", ctypes.c_uint32), ("count", ctypes.c_uint32), ("device", ctypes.c_int), ("rc", ctypes.c_int),
+                ("stats", DecodeStats)]
+
+    def as_dict(self):
+        return dict(first=self.first, count=self.count, device=self.device, rc=self.rc, stats=self.stats.as_dict())
+
+
+class DecodeMultiStats(ctypes.Structure):
+    """lfm_decode_multi_stats (lfm_api.h)."""
+    _fields_ = [("total_ms", ctypes.c_double), ("axis", ctypes.c_int), ("workers", ctypes.c_int),
+                ("blocks", ctypes.c_uint64), ("host_blocks", ctypes.c_uint64), ("d2h_bytes", ctypes.c_uint64)]
 
     def as_dict(self):
         return {f: getattr(self, f) for f, _ in self._fields_}
@@ -176,6 +196,28 @@ def lib():
                                                    ctypes.POINTER(DecodeStats)]
     if hasattr(L, "lfm_hip_crop_region"):
         L.lfm_hip_crop_region.argtypes = [vp, u32p, u32p, u32p, ctypes.c_uint32, vp, vp]
+    # the multi-GPU reader, likewise
+    intp = ctypes.POINTER(ctypes.c_int)
+    if hasattr(L, "lfm_set_decode_devices"):
+        L.lfm_set_decode_devices.argtypes = [intp, ctypes.c_int]
+    if hasattr(L, "lfm_get_decode_devices"):
+        L.lfm_get_decode_devices.argtypes = [intp, ctypes.c_int]
+    if hasattr(L, "lfm_default_decode_devices"):
+        L.lfm_default_decode_devices.argtypes = [ctypes.c_int, intp, ctypes.c_int]
+    if hasattr(L, "lfm_release_decoders"):
+        L.lfm_release_decoders.argtypes = []
+        L.lfm_release_decoders.restype = None
+    if hasattr(L, "lfm_decode_shard_plan"):
+        L.lfm_decode_shard_plan.argtypes = [vp, ctypes.c_uint64, ctypes.c_int, intp, u32p, u32p, ctypes.c_int]
+    if hasattr(L, "lfm_decode_memory_multi"):
+        L.lfm_decode_memory_multi.argtypes = [vp, ctypes.c_uint64, vp, ctypes.c_int,
+                                              ctypes.POINTER(DecodeMultiStats), ctypes.POINTER(DecodeShard),
+                                              ctypes.c_int]
+    if hasattr(L, "lfm_decode_memory_multi_device"):
+        L.lfm_decode_memory_multi_device.argtypes = [vp, ctypes.c_uint64, ctypes.POINTER(vp),
+                                                     ctypes.POINTER(ctypes.c_uint64), ctypes.c_int, ctypes.c_int,
+                                                     ctypes.POINTER(DecodeMultiStats), ctypes.POINTER(DecodeShard),
+                                                     ctypes.c_int]
     _lib = L
     return L
 
@@ -648,6 +690,113 @@ def read_lfm_device(path, out=None, device=None, num_threads=-1, return_stats=Fa
     with open(path, "rb") as f:
         buf = f.read()
     return decode_device(buf, out=out, device=device, num_threads=num_threads, return_stats=return_stats)
+
+
+# ------------------------------------------------------- multi-GPU reader --
+def set_decode_devices(devices=None):
+    """Devices the whole-image readers farm block-layer ranges to
+    (lfm_set_decode_devices; a device may repeat); None or [] restores the
+    default: env LFM_DECODE_GPUS, empty without it.  Fewer than two entries:
+    every reader runs on the current device as ever."""
+    devices = list(devices or [])
+    arr = (ctypes.c_int * max(1, len(devices)))(*devices)
+    _check(_need("lfm_set_decode_devices")(arr, len(devices)), "lfm_set_decode_devices")
+
+
+def get_decode_devices():
+    arr = (ctypes.c_int * 256)()
+    n = _need("lfm_get_decode_devices")(arr, 256)
+    return list(arr[:min(n, 256)])
+
+
+def default_decode_devices(n_visible):
+    """env LFM_DECODE_GPUS parsed for n_visible devices (no device call)."""
+    arr = (ctypes.c_int * 256)()
+    n = _need("lfm_default_decode_devices")(int(n_visible), arr, 256)
+    return list(arr[:min(n, 256)])
+
+
+def release_decoders():
+    """End the readers' kept workers; their device / pinned buffers are freed."""
+    _need("lfm_release_decoders")()
+
+
+def decode_shard_plan(buf, n):
+    """(axis, [(first, count), ...]) of lfm_decode_shard_plan: how the file is
+    cut for n workers, along xyzct index `axis`."""
+    fn = _need("lfm_decode_shard_plan")
+    axis = ctypes.c_int()
+    cap = max(1, int(n))
+    first, count = (ctypes.c_uint32 * cap)(), (ctypes.c_uint32 * cap)()
+    s = fn(_addr(buf), len(buf), int(n), ctypes.byref(axis), first, count, cap)
+    if s <= 0:
+        raise LfmError("lfm_decode_shard_plan: the buffer holds no .lfm header")
+    return axis.value, [(first[w], count[w]) for w in range(min(s, cap))]
+
+
+def _multi_stats(st, shards, n):
+    d = st.as_dict()
+    d["shards"] = [shards[w].as_dict() for w in range(min(max(st.workers, 0), n))]
+    return d
+
+
+def decode_multi(buf, num_threads=-1, return_stats=False):
+    """lfm_decode_memory_multi: decode an in-memory .lfm into a numpy array
+    [t, c, z, y, x] with one worker per entry of the decode device list
+    (set_decode_devices); with return_stats also the lfm_decode_multi_stats as
+    a dict, its "shards" the list of lfm_decode_shard dicts."""
+    fn = _need("lfm_decode_memory_multi")
+    xyzct, dt = _device_header(buf, "decode_multi")
+    out = np.empty(tuple(xyzct[::-1]), dtype=NP_OF[dt])
+    st = DecodeMultiStats()
+    cap = max(1, len(get_decode_devices()))
+    shards = (DecodeShard * cap)()
+    _check(fn(_addr(buf), len(buf), out.ctypes.data, num_threads, ctypes.byref(st), shards, cap),
+           "lfm_decode_memory_multi")
+    return (out, _multi_stats(st, shards, cap)) if return_stats else out
+
+
+def decode_device_sharded(buf, devices=None, outs=None, return_stats=False):
+    """lfm_decode_memory_multi_device: decode an in-memory .lfm into one torch
+    CUDA tensor per shard, each on its own device, side by side.  devices: one
+    CUDA device per worker (default: the decode device list, else the current
+    device); the file is cut as decode_shard_plan(buf, len(devices)) says and
+    shard w lands on devices[w].  outs: the tensors to decode into instead,
+    one per shard of decode_shard_plan(buf, len(outs)), each the shard's size.
+    Returns (axis, [(first, tensor), ...]), the tensors shaped [t, c, z, y, x]
+    with the shard's extent along xyzct index `axis`; with return_stats also
+    the stats dict of decode_multi.  Ordering per tensor as decode_device."""
+    fn = _need("lfm_decode_memory_multi_device")
+    xyzct, dt = _device_header(buf, "decode_device_sharded")
+    if not _HAVE_TORCH:
+        raise LfmError("decode_device_sharded needs PyTorch")
+    if outs is not None:
+        n = len(outs)
+    else:
+        if devices is None:
+            devices = get_decode_devices() or [torch.cuda.current_device()]
+        devices = [torch.device("cuda", d) if isinstance(d, int) else torch.device(d) for d in devices]
+        n = len(devices)
+    if n < 1:
+        raise ValueError("decode_device_sharded: no destination")
+    axis, plan = decode_shard_plan(buf, n)
+    if outs is not None and len(plan) != n:
+        raise ValueError("decode_device_sharded: %d tensors, but %d workers get %d shards" % (n, n, len(plan)))
+    tensors = []
+    for w, (first, count) in enumerate(plan):
+        shape = xyzct[::-1]
+        shape[4 - axis] = count
+        tensors.append(_device_out("decode_device_sharded", dt, shape, None if outs is None else outs[w],
+                                   None if outs is not None else devices[w]))
+    S = len(tensors)
+    ptrs = (ctypes.c_void_p * S)(*[t.data_ptr() for t in tensors])
+    sizes = (ctypes.c_uint64 * S)(*[t.numel() * t.element_size() for t in tensors])
+    st = DecodeMultiStats()
+    shards = (DecodeShard * S)()
+    _check(fn(_addr(buf), len(buf), ptrs, sizes, S, -1, ctypes.byref(st), shards, S),
+           "lfm_decode_memory_multi_device")
+    res = (axis, [(first, t) for (first, _), t in zip(plan, tensors)])
+    return res + (_multi_stats(st, shards, S),) if return_stats else res
 
 
 # ------------------------------------------------------ device primitives --
