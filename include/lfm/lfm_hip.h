@@ -61,6 +61,12 @@ int lfm_hip_unpredict_async(const uint16_t* d_sym, const uint16_t* d_prev, uint1
  * hand-over timeout repaired on the device, reported on stderr), else
  * LFM_HIP_ERUNTIME. */
 int lfm_hip_unpredict_check(int status);
+/* Which kernel lfm_hip_unpredict runs for W x H frames of lenslet size T:
+ * 0 the chain (one wave per 64-row band, bands hand rows over in memory),
+ * 1 the frame wave (one wave per frame, the band above's rows kept in LDS),
+ * 2 the one-wave kernel (rows of earlier bands from memory); -1 for
+ * T <= 0, T > 31, W <= 0 or H <= 0.  Pure: no HIP call. */
+int lfm_hip_unpredict_path(int W, int H, int T);
 
 /* The seven spatial candidates of one frame (predictors 1..7, symbolized) in
  * one launch: candidate k goes to d_out7 + (k-1)*W*H. */

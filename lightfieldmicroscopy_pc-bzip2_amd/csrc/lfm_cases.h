@@ -8,6 +8,7 @@
 // checks these tables and formula spellings against the reference source text.
 #pragma once
 #include <cstdint>
+#include <type_traits>
 #include <hip/hip_runtime.h>
 
 namespace lfm {
@@ -33,6 +34,66 @@ enum Formula : int {
 
 enum TileCase : int { TC_00 = 0, TC_0Y = 1, TC_X0 = 2, TC_XY = 3 };
 enum PosCase : int { UC_COL = 0, UC_CORNER = 1, UC_ROW = 2, UC_IN = 3 };
+
+// the case of lenslet (tx, ty) = (x / T, y / T) and of position (u, v) = (x % T, y % T) in it
+__host__ __device__ __forceinline__ constexpr TileCase tile_case(int tx, int ty)
+{
+    return tx == 0 ? (ty == 0 ? TC_00 : TC_0Y) : (ty == 0 ? TC_X0 : TC_XY);
+}
+__host__ __device__ __forceinline__ constexpr PosCase pos_case(int u, int v)
+{
+    return u == 0 ? (v > 0 ? UC_COL : UC_CORNER) : (v == 0 ? UC_ROW : UC_IN);
+}
+
+// Where neighbour N sits relative to (x, y): the one offset table.  Every
+// accessor is "offset, then fetch from my storage".
+//   A (-1, 0)   B (0, -1)   C (-1, -1)   AP (-T, 0)   BP (0, -T)   CP (-T, -T)
+//   AP1 (-T-1, 0)   BP1 (0, -T-1)   ABP (-1, -T)   BAP (-T, -1)
+template <int N>
+__host__ __device__ __forceinline__ constexpr int nb_dx(int T)
+{
+    if constexpr (N == NB_A || N == NB_C || N == NB_ABP) return -1;
+    else if constexpr (N == NB_AP || N == NB_CP || N == NB_BAP) return -T;
+    else if constexpr (N == NB_AP1) return -(T + 1);
+    else return 0;
+}
+template <int N>
+__host__ __device__ __forceinline__ constexpr int nb_dy(int T)
+{
+    if constexpr (N == NB_B || N == NB_C || N == NB_BAP) return -1;
+    else if constexpr (N == NB_BP || N == NB_CP || N == NB_ABP) return -T;
+    else if constexpr (N == NB_BP1) return -(T + 1);
+    else return 0;
+}
+
+// neighbours straight from a frame in memory (the generic forward kernel and
+// the host inverse)
+struct GlobalNb {
+    const uint16_t* f;
+    int W, T, x, y;
+    template <int N>
+    __host__ __device__ __forceinline__ int at() const
+    {
+        return (int)f[(size_t)(y + nb_dy<N>(T)) * W + (x + nb_dx<N>(T))];
+    }
+};
+
+// Calls fn(integral_constant<int, tc>, integral_constant<int, uc>): the one
+// place a pixel's runtime case becomes the template arguments of its formula.
+template <class Fn>
+__host__ __device__ __forceinline__ int with_case(int tc, int uc, Fn&& fn)
+{
+    switch (tc * 4 + uc) {
+#define LFM_CASE(TC_, UC_) \
+    case TC_ * 4 + UC_: return fn(std::integral_constant<int, TC_>{}, std::integral_constant<int, UC_>{});
+    LFM_CASE(0, 0) LFM_CASE(0, 1) LFM_CASE(0, 2) LFM_CASE(0, 3)
+    LFM_CASE(1, 0) LFM_CASE(1, 1) LFM_CASE(1, 2) LFM_CASE(1, 3)
+    LFM_CASE(2, 0) LFM_CASE(2, 1) LFM_CASE(2, 2) LFM_CASE(2, 3)
+    LFM_CASE(3, 0) LFM_CASE(3, 1) LFM_CASE(3, 2) LFM_CASE(3, 3)
+#undef LFM_CASE
+    }
+    return 0;
+}
 
 // [predictor-1][tile case][position case]
 constexpr uint8_t kTiles[7][4][4] = {
@@ -193,6 +254,20 @@ __host__ __device__ __forceinline__ int case_residual(G& g, int I, int P)
             return ((I - eval_formula<F>(g)) + P) >> 1;
         }
     }
+}
+
+// The decoded pixel (before the uint16 store) of case (FAM, K, TC, UC) from
+// its unsymbolized residual r: the forward formula on DECODED neighbours.
+// Temporal frames are tiles only (the angle / space temporal residual drops a
+// bit): I = r + ((pred + P) >> 1), or r + P where there is no prediction.
+template <int FAM, int K, int TC, int UC, bool TEMP, class G>
+__host__ __device__ __forceinline__ int inverse_case(G& g, int r, int P)
+{
+    constexpr int F = case_formula(FAM, K, TC, UC);
+    const int pr = eval_formula<F>(g);
+    if constexpr (!TEMP) return r + pr;
+    else if constexpr (F == F_Z) return r + P;
+    else return r + ((pr + P) >> 1);
 }
 
 // How a case turns its prediction into the residual (as case_residual above):

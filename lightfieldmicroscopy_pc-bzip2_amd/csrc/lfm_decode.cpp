@@ -18,58 +18,17 @@ namespace lfm {
 
 // ---------------------------------------------------------------- decode --
 namespace {
-struct HostNb {
-    const uint16_t* f;
-    int W, T, x, y;
-    template <int N>
-    int at() const
-    {
-        int dx = 0, dy = 0;
-        if constexpr (N == NB_A) { dx = -1; }
-        if constexpr (N == NB_B) { dy = -1; }
-        if constexpr (N == NB_C) { dx = -1; dy = -1; }
-        if constexpr (N == NB_AP) { dx = -T; }
-        if constexpr (N == NB_BP) { dy = -T; }
-        if constexpr (N == NB_CP) { dx = -T; dy = -T; }
-        if constexpr (N == NB_AP1) { dx = -T - 1; }
-        if constexpr (N == NB_BP1) { dy = -T - 1; }
-        if constexpr (N == NB_ABP) { dx = -1; dy = -T; }
-        if constexpr (N == NB_BAP) { dx = -T; dy = -1; }
-        return (int)f[(size_t)(y + dy) * W + (x + dx)];
-    }
-};
-
-// prediction (spatial) or temporal prediction of the tiles family for a case
-template <int FAM, int K, int TC, int UC, bool TEMP>
-inline int inv_case(HostNb& g, int r, int P)
-{
-    constexpr int F = case_formula(FAM, K, TC, UC);
-    const int pr = eval_formula<F>(g);
-    if constexpr (!TEMP) return r + pr;
-    else if constexpr (F == F_Z) return r + P;
-    else return r + ((pr + P) >> 1);  // tiles: I = r + ((pred + P) >> 1)
-}
-
 template <int FAM, int K, bool TEMP>
 void unpredict_frame(const uint16_t* sym, const uint16_t* prev, uint16_t* out, int W, int H, int T)
 {
     for (int y = 0; y < H; ++y)
         for (int x = 0; x < W; ++x) {
-            HostNb g{out, W, T, x, y};
-            const int tx = x / T, ty = y / T, u = x % T, v = y % T;
-            const int tc = tx == 0 ? (ty == 0 ? 0 : 1) : (ty == 0 ? 2 : 3);
-            const int uc = u == 0 ? (v > 0 ? 0 : 1) : (v == 0 ? 2 : 3);
+            GlobalNb g{out, W, T, x, y};
             const int r = unsymbolize16(sym[(size_t)y * W + x]);
             const int P = TEMP ? (int)prev[(size_t)y * W + x] : 0;
-            int val = 0;
-            switch (tc * 4 + uc) {
-#define LFM_INV(TC_, UC_) case TC_ * 4 + UC_: val = inv_case<FAM, K, TC_, UC_, TEMP>(g, r, P); break;
-            LFM_INV(0, 0) LFM_INV(0, 1) LFM_INV(0, 2) LFM_INV(0, 3)
-            LFM_INV(1, 0) LFM_INV(1, 1) LFM_INV(1, 2) LFM_INV(1, 3)
-            LFM_INV(2, 0) LFM_INV(2, 1) LFM_INV(2, 2) LFM_INV(2, 3)
-            LFM_INV(3, 0) LFM_INV(3, 1) LFM_INV(3, 2) LFM_INV(3, 3)
-#undef LFM_INV
-            }
+            const int val = with_case(tile_case(x / T, y / T), pos_case(x % T, y % T), [&](auto TC, auto UC) {
+                return inverse_case<FAM, K, TC.value, UC.value, TEMP>(g, r, P);
+            });
             out[(size_t)y * W + x] = (uint16_t)val;
         }
 }

@@ -65,44 +65,12 @@ __device__ __forceinline__ const uint16_t* frame_prev(const FrameSet& p, int fz)
 }
 
 // ----------------------------------------------------------- generic path --
-struct GlobalNb {
-    const uint16_t* f;
-    int W, T, x, y;
-    template <int N>
-    __device__ __forceinline__ int at() const
-    {
-        int dx = 0, dy = 0;
-        if constexpr (N == NB_A) { dx = -1; }
-        if constexpr (N == NB_B) { dy = -1; }
-        if constexpr (N == NB_C) { dx = -1; dy = -1; }
-        if constexpr (N == NB_AP) { dx = -T; }
-        if constexpr (N == NB_BP) { dy = -T; }
-        if constexpr (N == NB_CP) { dx = -T; dy = -T; }
-        if constexpr (N == NB_AP1) { dx = -T - 1; }
-        if constexpr (N == NB_BP1) { dy = -T - 1; }
-        if constexpr (N == NB_ABP) { dx = -1; dy = -T; }
-        if constexpr (N == NB_BAP) { dx = -T; dy = -1; }
-        return (int)f[(size_t)(y + dy) * W + (x + dx)];
-    }
-};
-
+// the residual of a pixel whose case is known only at run time
 template <int FAM, int K, bool TEMP, class G>
 __device__ __forceinline__ int residual_any_case(G& g, int tc, int uc, int I, int P)
 {
-    switch (tc * 4 + uc) {
-#define LFM_CASE(TC_, UC_) \
-    case TC_ * 4 + UC_: return case_residual<FAM, K, TC_, UC_, TEMP>(g, I, P);
-    LFM_CASE(0, 0) LFM_CASE(0, 1) LFM_CASE(0, 2) LFM_CASE(0, 3)
-    LFM_CASE(1, 0) LFM_CASE(1, 1) LFM_CASE(1, 2) LFM_CASE(1, 3)
-    LFM_CASE(2, 0) LFM_CASE(2, 1) LFM_CASE(2, 2) LFM_CASE(2, 3)
-    LFM_CASE(3, 0) LFM_CASE(3, 1) LFM_CASE(3, 2) LFM_CASE(3, 3)
-#undef LFM_CASE
-    }
-    return 0;
+    return with_case(tc, uc, [&](auto TC, auto UC) { return case_residual<FAM, K, TC.value, UC.value, TEMP>(g, I, P); });
 }
-
-__device__ __forceinline__ int tile_case(int tx, int ty) { return tx == 0 ? (ty == 0 ? 0 : 1) : (ty == 0 ? 2 : 3); }
-__device__ __forceinline__ int pos_case(int u, int v) { return u == 0 ? (v > 0 ? 0 : 1) : (v == 0 ? 2 : 3); }
 
 // One thread per pixel, neighbours straight from global memory (any W, any T).
 template <int FAM, int K>

@@ -18,6 +18,18 @@
 // come from the output in memory.  All 64 rows move in lock step (one wave),
 // so no barrier is needed; frames are independent (even frames first, then
 // odd temporal frames on their decoded predecessors).
+//
+// Three kernels run that wavefront; choose_path picks one per call:
+//
+//   path        kernel           shapes                         LDS, waves
+//   chain       unpredict_band5  T 2..30, W % 8 == 0, H > 64,   8 KiB + (T+1) * 256 B per band;
+//                                frame < 2 GiB, and the         one wave per (band, frame),
+//                                frame wave's LDS fits          bands hand rows over in memory
+//   frame wave  unpredict_band3  T 2..30 otherwise, while       8 KiB + (T+1) * W * 2 B <= 160 KiB;
+//                                its LDS fits                   one wave per frame
+//   one wave    unpredict_band   T == 1, T == 31, wider frames; 8 KiB; one wave per frame
+//                                the re-run after a chain
+//                                hand-over gave up
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <climits>
@@ -40,32 +52,12 @@ struct BandNb {
     template <int N>
     __device__ __forceinline__ int at() const
     {
-        int dx = 0, dy = 0;
-        if constexpr (N == NB_A) { dx = -1; }
-        if constexpr (N == NB_B) { dy = -1; }
-        if constexpr (N == NB_C) { dx = -1; dy = -1; }
-        if constexpr (N == NB_AP) { dx = -T; }
-        if constexpr (N == NB_BP) { dy = -T; }
-        if constexpr (N == NB_CP) { dx = -T; dy = -T; }
-        if constexpr (N == NB_AP1) { dx = -T - 1; }
-        if constexpr (N == NB_BP1) { dy = -T - 1; }
-        if constexpr (N == NB_ABP) { dx = -1; dy = -T; }
-        if constexpr (N == NB_BAP) { dx = -T; dy = -1; }
+        const int dx = nb_dx<N>(T), dy = nb_dy<N>(T);
         const int rr = r + dy;
         if (rr >= 0) return ring[rr * kRing + ((x + dx) & (kRing - 1))];
         return out[(size_t)(y + dy) * W + (x + dx)];
     }
 };
-
-template <int FAM, int K, int TC, int UC, bool TEMP>
-__device__ __forceinline__ int inv_case(BandNb& g, int r, int P)
-{
-    constexpr int F = case_formula(FAM, K, TC, UC);
-    const int pr = eval_formula<F>(g);
-    if constexpr (!TEMP) return r + pr;
-    else if constexpr (F == F_Z) return r + P;
-    else return r + ((pr + P) >> 1);
-}
 
 struct UnFrames {
     const uint16_t* sym;   // nz frames of symbols
@@ -117,30 +109,18 @@ __global__ __launch_bounds__(64) void unpredict_band(UnFrames p)
             const int x = k - r;
             if (row_ok && x >= 0 && x < W) {
                 BandNb g{ring, out, W, T, x, y, r};
-                const int tc = tx == 0 ? (ty == 0 ? TC_00 : TC_0Y) : (ty == 0 ? TC_X0 : TC_XY);
-                const int uc = u == 0 ? (v > 0 ? UC_COL : UC_CORNER) : (v == 0 ? UC_ROW : UC_IN);
+                const int tc = tile_case(tx, ty), uc = pos_case(u, v);
                 const int res = unsymbolize16(sym[(size_t)y * W + x]);
                 const int P = temporal ? (int)prev[(size_t)y * W + x] : 0;
-                int val = 0;
-                if (temporal) {
-                    switch (tc * 4 + uc) {
-#define LFM_INV(TC_, UC_) case TC_ * 4 + UC_: val = inv_case<FAM, K, TC_, UC_, true>(g, res, P); break;
-                    LFM_INV(0, 0) LFM_INV(0, 1) LFM_INV(0, 2) LFM_INV(0, 3)
-                    LFM_INV(1, 0) LFM_INV(1, 1) LFM_INV(1, 2) LFM_INV(1, 3)
-                    LFM_INV(2, 0) LFM_INV(2, 1) LFM_INV(2, 2) LFM_INV(2, 3)
-                    LFM_INV(3, 0) LFM_INV(3, 1) LFM_INV(3, 2) LFM_INV(3, 3)
-#undef LFM_INV
-                    }
-                } else {
-                    switch (tc * 4 + uc) {
-#define LFM_INV(TC_, UC_) case TC_ * 4 + UC_: val = inv_case<FAM, K, TC_, UC_, false>(g, res, P); break;
-                    LFM_INV(0, 0) LFM_INV(0, 1) LFM_INV(0, 2) LFM_INV(0, 3)
-                    LFM_INV(1, 0) LFM_INV(1, 1) LFM_INV(1, 2) LFM_INV(1, 3)
-                    LFM_INV(2, 0) LFM_INV(2, 1) LFM_INV(2, 2) LFM_INV(2, 3)
-                    LFM_INV(3, 0) LFM_INV(3, 1) LFM_INV(3, 2) LFM_INV(3, 3)
-#undef LFM_INV
-                    }
-                }
+                int val;
+                if (temporal)
+                    val = with_case(tc, uc, [&](auto TC, auto UC) {
+                        return inverse_case<FAM, K, TC.value, UC.value, true>(g, res, P);
+                    });
+                else
+                    val = with_case(tc, uc, [&](auto TC, auto UC) {
+                        return inverse_case<FAM, K, TC.value, UC.value, false>(g, res, P);
+                    });
                 const uint16_t o = (uint16_t)val;
                 ring[r * kRing + (x & (kRing - 1))] = o;
                 out[(size_t)y * W + x] = o;
@@ -157,174 +137,67 @@ __global__ __launch_bounds__(64) void unpredict_band(UnFrames p)
     }
 }
 
-// Same band wavefront with the latency taken out of a step: the previous
-// band's last T+1 rows stay in LDS at full width (`top`, overwritten in place
-// by this band's last T+1 rows: a column is rewritten at least 64 - 2(T+1)
-// steps after its last reader, so T <= 30), and each lane's symbols are
-// loaded 8 steps ahead (a register delay line).  No global load on the
-// dependency chain of a step; 64 + (T+1) * W * 2 B of LDS per frame.
-struct BandNb2 {
-    const uint16_t* ring;  // [64 rows][kRing]
-    const uint16_t* top;   // [T + 1 rows][W]: rows y0 - T - 1 .. y0 - 1
-    int W, TT, x, r;
-    template <int N>
-    __device__ __forceinline__ int at() const
-    {
-        int dx = 0, dy = 0;
-        if constexpr (N == NB_A) { dx = -1; }
-        if constexpr (N == NB_B) { dy = -1; }
-        if constexpr (N == NB_C) { dx = -1; dy = -1; }
-        if constexpr (N == NB_AP) { dx = -(TT - 1); }
-        if constexpr (N == NB_BP) { dy = -(TT - 1); }
-        if constexpr (N == NB_CP) { dx = -(TT - 1); dy = -(TT - 1); }
-        if constexpr (N == NB_AP1) { dx = -TT; }
-        if constexpr (N == NB_BP1) { dy = -TT; }
-        if constexpr (N == NB_ABP) { dx = -1; dy = -(TT - 1); }
-        if constexpr (N == NB_BAP) { dx = -(TT - 1); dy = -1; }
-        const int rr = r + dy;
-        if (rr >= 0) return ring[rr * kRing + ((x + dx) & (kRing - 1))];
-        return top[(TT + rr) * W + (x + dx)];
-    }
-};
-
-template <int FAM, int K, int TC, int UC, bool TEMP>
-__device__ __forceinline__ int inv_case2(BandNb2& g, int r, int P)
-{
-    constexpr int F = case_formula(FAM, K, TC, UC);
-    const int pr = eval_formula<F>(g);
-    if constexpr (!TEMP) return r + pr;
-    else if constexpr (F == F_Z) return r + P;
-    else return r + ((pr + P) >> 1);
-}
-
-template <int FAM, int K, bool TEMP>
-__device__ __forceinline__ int inv_any2(BandNb2& g, int tc, int uc, int res, int P)
-{
-    switch (tc * 4 + uc) {
-#define LFM_INV(TC_, UC_) case TC_ * 4 + UC_: return inv_case2<FAM, K, TC_, UC_, TEMP>(g, res, P);
-    LFM_INV(0, 0) LFM_INV(0, 1) LFM_INV(0, 2) LFM_INV(0, 3)
-    LFM_INV(1, 0) LFM_INV(1, 1) LFM_INV(1, 2) LFM_INV(1, 3)
-    LFM_INV(2, 0) LFM_INV(2, 1) LFM_INV(2, 2) LFM_INV(2, 3)
-    LFM_INV(3, 0) LFM_INV(3, 1) LFM_INV(3, 2) LFM_INV(3, 3)
-#undef LFM_INV
-    }
-    return 0;
-}
-
+// The frame wave (unpredict_band3): the band wavefront with the latency
+// taken out of a step.  The previous band's last T+1 rows stay in LDS at full
+// width (`top`, overwritten in place by this band's last T+1 rows: a column is
+// rewritten at least 64 - 2(T+1) steps after its last reader, so T <= 30), and
+// each lane's symbols are loaded kSymAhead steps ahead (a register delay
+// line): no global load on the dependency chain of a step.  The neighbours
+// one step away come from registers: A = this lane's previous result, B / C =
+// row r - 1's previous / second-previous result moved over by a DPP lane
+// shift (row 0 takes them from `top`); every other neighbour was produced at
+// least T steps earlier (T >= 2) and is read from LDS before the step's own
+// writes.  Outside the first band and the first T + 63 steps of a band every
+// lane is in the interior tile case, so the four position-case formulas are
+// all evaluated and one is selected per lane (no divergent case switch); edge
+// steps evaluate all sixteen cases and select.
 constexpr int kSymAhead = 8;
 
-template <int FAM, int K, bool TEMP>
-__device__ __forceinline__ void band2(const UnFrames& p, int fz, uint16_t* ring, uint16_t* top)
-{
-    const int r = threadIdx.x;
-    const size_t fs = (size_t)p.W * p.H;
-    const uint16_t* sym = p.sym + fz * fs;
-    uint16_t* out = p.out + fz * fs;
-    const uint16_t* prev = TEMP ? (fz ? p.out + (fz - 1) * fs : p.prev) : nullptr;
-    const int W = p.W, H = p.H, T = p.T, TT = T + 1, tb = 64 - TT;
-    for (int y0 = 0; y0 < H; y0 += 64) {
-        const int y = y0 + r;
-        const bool row_ok = y < H;
-        const int v = y % T, ty = y / T;
-        const uint16_t* srow = sym + (size_t)(row_ok ? y : 0) * W;
-        const uint16_t* prow = TEMP ? prev + (size_t)(row_ok ? y : 0) * W : nullptr;
-        uint16_t* orow = out + (size_t)(row_ok ? y : 0) * W;
-        uint16_t* trow = top + (r >= tb ? r - tb : 0) * W;
-        // delay line: sq[j] holds the symbol (and previous-frame pixel) of
-        // column k - r for the step k = k0 + j of the current round
-        uint32_t sq[kSymAhead];
-#pragma unroll
-        for (int j = 0; j < kSymAhead; ++j) {
-            const int x = j - r;
-            uint32_t sv = 0;
-            if (row_ok && x >= 0 && x < W) {
-                sv = srow[x];
-                if (TEMP) sv |= (uint32_t)prow[x] << 16;
-            }
-            sq[j] = sv;
-        }
-        int u = 0, tx = 0;  // x % T and x / T, advanced with x
-        for (int k0 = 0; k0 < W + 63; k0 += kSymAhead) {
-#pragma unroll
-            for (int j = 0; j < kSymAhead; ++j) {
-                const int k = k0 + j;
-                const int x = k - r;
-                const uint32_t sv = sq[j];
-                {  // the load for step k + kSymAhead (column x + kSymAhead)
-                    const int xn = x + kSymAhead;
-                    uint32_t nv = 0;
-                    if (row_ok && xn >= 0 && xn < W) {
-                        nv = srow[xn];
-                        if (TEMP) nv |= (uint32_t)prow[xn] << 16;
-                    }
-                    sq[j] = nv;
-                }
-                if (row_ok && x >= 0 && x < W) {
-                    BandNb2 g{ring, top, W, TT, x, r};
-                    const int tc = tx == 0 ? (ty == 0 ? TC_00 : TC_0Y) : (ty == 0 ? TC_X0 : TC_XY);
-                    const int uc = u == 0 ? (v > 0 ? UC_COL : UC_CORNER) : (v == 0 ? UC_ROW : UC_IN);
-                    const int res = unsymbolize16(sv & 0xFFFFu);
-                    const int val = inv_any2<FAM, K, TEMP>(g, tc, uc, res, TEMP ? (int)(sv >> 16) : 0);
-                    const uint16_t o = (uint16_t)val;
-                    ring[r * kRing + (x & (kRing - 1))] = o;
-                    orow[x] = o;
-                    if (r >= tb) trow[x] = o;
-                    if (++u == T) {
-                        u = 0;
-                        ++tx;
-                    }
-                }
-            }
-        }
-    }
-}
-
-// band3: the band2 wavefront with the step's dependency chain cut down to
-// registers.  The neighbours one step away come from registers: A = this
-// lane's previous result, B / C = row r - 1's previous / second-previous
-// result moved over by a DPP lane shift (row 0 takes them from `top`); every
-// other neighbour was produced at least T steps earlier and is read from LDS
-// before the step's own writes.  Outside the first band and the first T + 63
-// steps of a band every lane is in the interior tile case, so the four
-// position-case formulas are all evaluated and one is selected per lane (no
-// divergent case switch); edge steps evaluate all sixteen cases and select.
 struct NbVals {
     int v[NB_COUNT];
     template <int N>
     __device__ __forceinline__ int at() const { return v[N]; }
 };
 
-template <int FAM, int K, int TC, int UC, bool TEMP>
-__device__ __forceinline__ int inv_case3(NbVals& g, int r, int P)
+// the seven neighbours at least T steps old: fetch(dx, dy) reads (x + dx, y + dy) from LDS
+template <int N, class Fetch>
+__device__ __forceinline__ void load_far_nb(NbVals& f, int T, Fetch& fetch)
 {
-    constexpr int F = case_formula(FAM, K, TC, UC);
-    const int pr = eval_formula<F>(g);
-    if constexpr (!TEMP) return r + pr;
-    else if constexpr (F == F_Z) return r + P;
-    else return r + ((pr + P) >> 1);
+    f.v[N] = fetch(nb_dx<N>(T), nb_dy<N>(T));
+}
+template <class Fetch>
+__device__ __forceinline__ void load_far_nbs(NbVals& f, int T, Fetch fetch)
+{
+    load_far_nb<NB_AP>(f, T, fetch);
+    load_far_nb<NB_BP>(f, T, fetch);
+    load_far_nb<NB_CP>(f, T, fetch);
+    load_far_nb<NB_AP1>(f, T, fetch);
+    load_far_nb<NB_BP1>(f, T, fetch);
+    load_far_nb<NB_ABP>(f, T, fetch);
+    load_far_nb<NB_BAP>(f, T, fetch);
 }
 
 // the four position cases of tile case TC, evaluated branch-free and
 // selected per lane (u = x % T, v = y % T)
 template <int FAM, int K, int TC, bool TEMP>
-__device__ __forceinline__ int inv_tile3(NbVals& g, int res, int P, int u, int v)
+__device__ __forceinline__ int inv_tile(NbVals& g, int res, int P, int u, int v)
 {
-    const int vc = inv_case3<FAM, K, TC, UC_COL, TEMP>(g, res, P);
-    const int vk = inv_case3<FAM, K, TC, UC_CORNER, TEMP>(g, res, P);
-    const int vr = inv_case3<FAM, K, TC, UC_ROW, TEMP>(g, res, P);
-    const int vi = inv_case3<FAM, K, TC, UC_IN, TEMP>(g, res, P);
+    const int vc = inverse_case<FAM, K, TC, UC_COL, TEMP>(g, res, P);
+    const int vk = inverse_case<FAM, K, TC, UC_CORNER, TEMP>(g, res, P);
+    const int vr = inverse_case<FAM, K, TC, UC_ROW, TEMP>(g, res, P);
+    const int vi = inverse_case<FAM, K, TC, UC_IN, TEMP>(g, res, P);
     return u == 0 ? (v > 0 ? vc : vk) : (v == 0 ? vr : vi);
 }
 
 // every tile case (edge steps: x < T in some lane, or the frame's first band)
 template <int FAM, int K, bool TEMP>
-__device__ __forceinline__ int inv_edge3(NbVals& g, int res, int P, int u, int v, int tx, int ty, bool all_x)
+__device__ __forceinline__ int inv_edge(NbVals& g, int res, int P, int u, int v, int tx, int ty, bool all_x)
 {
-    const int vxy = inv_tile3<FAM, K, TC_XY, TEMP>(g, res, P, u, v);
-    const int vx0 = inv_tile3<FAM, K, TC_X0, TEMP>(g, res, P, u, v);
+    const int vxy = inv_tile<FAM, K, TC_XY, TEMP>(g, res, P, u, v);
+    const int vx0 = inv_tile<FAM, K, TC_X0, TEMP>(g, res, P, u, v);
     if (all_x) return ty == 0 ? vx0 : vxy;  // no lane has x < T
-    const int v0y = inv_tile3<FAM, K, TC_0Y, TEMP>(g, res, P, u, v);
-    const int v00 = inv_tile3<FAM, K, TC_00, TEMP>(g, res, P, u, v);
+    const int v0y = inv_tile<FAM, K, TC_0Y, TEMP>(g, res, P, u, v);
+    const int v00 = inv_tile<FAM, K, TC_00, TEMP>(g, res, P, u, v);
     return tx == 0 ? (ty == 0 ? v00 : v0y) : (ty == 0 ? vx0 : vxy);
 }
 
@@ -366,13 +239,7 @@ __device__ __forceinline__ void band3(const UnFrames& p, int fz, uint16_t* ring,
         auto load_far = [&](NbVals& f, int x) {
             f.v[NB_B] = r == 0 && x >= 0 ? (int)btop[x] : 0;
             f.v[NB_C] = r == 0 && x >= 1 ? (int)btop[x - 1] : 0;
-            f.v[NB_AP] = ring[far(x, -T, 0)];
-            f.v[NB_BP] = ring[far(x, 0, -T)];
-            f.v[NB_CP] = ring[far(x, -T, -T)];
-            f.v[NB_AP1] = ring[far(x, -TT, 0)];
-            f.v[NB_BP1] = ring[far(x, 0, -TT)];
-            f.v[NB_ABP] = ring[far(x, -1, -T)];
-            f.v[NB_BAP] = ring[far(x, -T, -1)];
+            load_far_nbs(f, T, [&](int dx, int dy) { return (int)ring[far(x, dx, dy)]; });
         };
         NbVals nf;
         nf.v[NB_A] = 0;
@@ -401,8 +268,8 @@ __device__ __forceinline__ void band3(const UnFrames& p, int fz, uint16_t* ring,
                 const int res = unsymbolize16(sv);
                 const int P = TEMP ? (int)pv : 0;
                 int val;
-                if (k >= edge_k && y0 > 0) val = inv_tile3<FAM, K, TC_XY, TEMP>(g, res, P, u, v);
-                else val = inv_edge3<FAM, K, TEMP>(g, res, P, u, v, tx, ty, k >= edge_k);
+                if (k >= edge_k && y0 > 0) val = inv_tile<FAM, K, TC_XY, TEMP>(g, res, P, u, v);
+                else val = inv_edge<FAM, K, TEMP>(g, res, P, u, v, tx, ty, k >= edge_k);
                 const uint16_t o = (uint16_t)val;
                 if (ok) {
                     ring[r * kRing + (x & (kRing - 1))] = o;
@@ -420,39 +287,58 @@ __device__ __forceinline__ void band3(const UnFrames& p, int fz, uint16_t* ring,
     }
 }
 
-// band4: band3 with the bands of a frame pipelined over NW waves of one
-// workgroup (wave w takes bands w, w + NW, ...).  Each wave publishes its
-// progress (band * stride + steps done) in LDS every kSync steps, after its
-// global stores have completed.  The rows a band needs from the band above
-// (its last T+1 rows) are read from the output in memory, a round of kSync
-// columns at a time, two rounds ahead of their use (workgroup-scope loads: the
-// waves share the CU's write-through L1), into a private LDS ring of kHand
-// columns: a
-// wave only ever waits for the band above to be far enough ahead, so the
-// waits form a chain from the first band down and cannot deadlock.
+// The chain (unpredict_band5): the frame-wave step with the bands of a frame
+// pipelined over the whole chip, one single-wave workgroup per (band, frame).
+// A band publishes its progress (band * stride + steps done) every kSync
+// steps.  The rows it needs from the band above (that band's last T+1 rows)
+// are read from the output in memory, a round of kSync columns at a time, two
+// rounds ahead of their use, into a private LDS ring of kHand columns.  A band
+// only ever waits for the band above to be far enough ahead, so the waits form
+// a chain from the first band down and cannot deadlock.
+//
+// The hand-over is write-through, the one protocol of this file:
+//   * every output store is a 16-byte `sc1` buffer store;
+//   * they are drained (`s_waitcnt vmcnt`, hand-counted inside a band, 0 at
+//     its end) before the progress word is written, itself an `sc1` store;
+//   * the progress word and the band above's rows are read with `sc1` loads
+//     to registers.
+// So neither side needs an agent-scope fence.  A release fence is
+// `buffer_wbl2 sc1`, a write-back of the XCD's whole L2, and an acquire
+// `buffer_inv sc1`; fenced, every band paid both every 32 steps.  Progress is
+// monotonic, so a stale read can only under-report it: it delays a band,
+// never releases one early.
+//
+// HIP promises neither a dispatch order nor a workgroup -> XCD placement, so a
+// workgroup does not take its band from blockIdx: its first act is to draw a
+// ticket (an agent-scope atomic add on the control block) and it decodes band
+// ticket / nfr of frame ticket % nfr.  Tickets go out in the order the
+// workgroups actually started, so the band a workgroup waits for (ticket -
+// nfr) belongs to a workgroup that is already resident, and the chain of waits
+// always ends at a running band 0, wherever and whenever the workgroups were
+// placed.  Ticket and progress words (one per band, 0 before the launch) live
+// in the hipMalloc'd control block (MI355X_MICROARCH.md, visibility,
+// write-through form).
+//
+// band5_body still has the parameters of the in-workgroup pipeline it came
+// from: NW waves, wave wv taking bands wv, wv + NW, ..., LDS offsets of its
+// two rings.  unpredict_band5 passes NW = nbands and wv = its band, so the
+// band loop runs once and `prodw` is the band above.  Folding them away
+// changed the generated code of every instantiation, vector memory
+// instructions included, so they stay.
 constexpr int kHand = 128;
 constexpr int kSync = 32;
 
-// XCU (cross-CU, band5 below): every band is its own workgroup, so `pos` lives
-// in global memory and the progress words and the hand-over loads of the band
-// above's rows use agent scope instead of workgroup scope.  The hand-over is
-// write-through instead of fenced: every output store is a 16-byte `sc1`
-// buffer store, drained (`s_waitcnt vmcnt(0)`) before the progress word (an
-// `sc1` store) is written, and every load of another band's rows is an `sc1`
-// load to registers, so neither side needs an agent-scope fence (a release
-// fence is `buffer_wbl2 sc1`, a write-back of the XCD's whole L2, an acquire
-// `buffer_inv sc1`; band5 issued both every 32 steps of every band).
-template <int FAM, int K, bool TEMP, bool XCU = false>
-__device__ __forceinline__ void band4(const UnFrames& p, int fz, int NW, int wv, uint16_t* lds, int ring_off,
-                                      int hand_off, int* pos)
+template <int FAM, int K, bool TEMP>
+__device__ __forceinline__ void band5_body(const UnFrames& p, int fz, int NW, int wv, uint16_t* lds, int ring_off,
+                                           int hand_off, int* pos)
 {
-    constexpr int kScope = XCU ? __HIP_MEMORY_SCOPE_AGENT : __HIP_MEMORY_SCOPE_WORKGROUP;
+    constexpr int kScope = __HIP_MEMORY_SCOPE_AGENT;
     const int r = threadIdx.x & 63;
     const size_t fs = (size_t)p.W * p.H;
     const uint16_t* sym = p.sym + fz * fs;
     uint16_t* out = p.out + fz * fs;
-    // write-through stores of the frame (XCU): one descriptor per wave over
-    // the frame, built from wave-uniform values only
+    // write-through stores of the frame: one descriptor per wave over the
+    // frame, built from wave-uniform values only
     const __amdgpu_buffer_rsrc_t orsrc = __builtin_amdgcn_make_buffer_rsrc(
         out, /*stride*/ 0, (int)__builtin_amdgcn_readfirstlane((int)(fs * sizeof(uint16_t))), 0x00020000);
     const uint16_t* prev = TEMP ? (fz ? p.out + (fz - 1) * fs : p.prev) : nullptr;
@@ -460,17 +346,15 @@ __device__ __forceinline__ void band4(const UnFrames& p, int fz, int NW, int wv,
     const int nbands = (H + 63) / 64, kend = W + 63, stride = W + 64 + 3 * kSync;
     const int prodw = (wv + NW - 1) % NW;
     // (bounded in time: a wait that gives up sets its bit in *p.status -- the
-    // frames of a band5 launch are then re-run on the device -- and the band
-    // runs on without waiting; never a hang.)  Progress is monotonic, so a
-    // stale read can only under-report it: it delays a band, never releases
-    // one early.
-    // XCU: `seen` is the producer's progress as last read; a read is issued
+    // frames of the launch are then re-run on the device -- and the band runs
+    // on without waiting; never a hang.)
+    // `seen` is the band above's progress as last read; a read is issued
     // after every wait and consumed at the next one (a round later, so it has
     // returned), and a wait that `seen` already satisfies costs no load
     int seen = -1, pending = -1;
     bool dead = false;  // this band gave up waiting: later waits return at once
     auto wait_ge = [&](int need) {
-        if constexpr (XCU) seen = max(seen, __builtin_amdgcn_readfirstlane(pending));
+        seen = max(seen, __builtin_amdgcn_readfirstlane(pending));
         if (seen < need && !dead) {
             const uint64_t t0 = (uint64_t)wall_clock64();
             for (int spin = 1;; ++spin) {
@@ -481,18 +365,16 @@ __device__ __forceinline__ void band4(const UnFrames& p, int fz, int NW, int wv,
                     break;
                 }
                 if ((spin & 63) == 0) {
-                    if constexpr (XCU) {
-                        // another band gave up: this launch is re-run anyway
-                        if (__builtin_amdgcn_readfirstlane(
-                                __hip_atomic_load(p.status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) & p.err_bit) {
-                            dead = true;
-                            break;
-                        }
-                        // a long wait also drops this CU's cached lines (an
-                        // agent acquire), so no cache level can keep serving
-                        // an old progress word
-                        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+                    // another band gave up: this launch is re-run anyway
+                    if (__builtin_amdgcn_readfirstlane(
+                            __hip_atomic_load(p.status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) & p.err_bit) {
+                        dead = true;
+                        break;
                     }
+                    // a long wait also drops this CU's cached lines (an
+                    // agent acquire), so no cache level can keep serving
+                    // an old progress word
+                    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
                     if ((uint64_t)wall_clock64() - t0 > p.wait_ticks) {
                         dead = true;
                         break;
@@ -503,11 +385,10 @@ __device__ __forceinline__ void band4(const UnFrames& p, int fz, int NW, int wv,
             if (dead && r == 0)
                 __hip_atomic_fetch_or(p.status, p.err_bit, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
-        if constexpr (XCU) pending = __hip_atomic_load(pos + prodw, __ATOMIC_RELAXED, kScope);
-        // XCU: every later load of the band above's rows is an sc1 load
-        // (hload), so this only keeps the compiler from hoisting them
-        if constexpr (XCU) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        else __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+        pending = __hip_atomic_load(pos + prodw, __ATOMIC_RELAXED, kScope);
+        // every later load of the band above's rows is an sc1 load (hload),
+        // so this only keeps the compiler from hoisting them
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
     };
     auto far = [&](int x, int dx, int dy) -> int {
         const int rr = r + dy;
@@ -527,7 +408,7 @@ __device__ __forceinline__ void band4(const UnFrames& p, int fz, int NW, int wv,
         const int v = y % T, ty = y / T;
         const uint32_t* hsrc = (const uint32_t*)(out + (size_t)(b > 0 && hl ? y0 - TT + hr : 0) * W);
         auto hload = [&](int c0) {  // columns c0 + hc .. + 16 of the round starting at column c0
-#pragma unroll
+    #pragma unroll
             for (int q = 0; q < 8; ++q) {
                 const int c = min(c0 + hc + 2 * q, W - 2);
                 hv[q] = __hip_atomic_load(hsrc + (c >> 1), __ATOMIC_RELAXED, kScope);
@@ -535,7 +416,7 @@ __device__ __forceinline__ void band4(const UnFrames& p, int fz, int NW, int wv,
         };
         auto hstore = [&](int c0) {
             if (hl) {
-#pragma unroll
+    #pragma unroll
                 for (int q = 0; q < 8; ++q)
                     *(uint32_t*)(lds + hand_off + hr * kHand + ((c0 + hc + 2 * q) & (kHand - 1))) = hv[q];
             }
@@ -567,7 +448,7 @@ __device__ __forceinline__ void band4(const UnFrames& p, int fz, int NW, int wv,
         };
         const int gbase = (0 - r) >> 3;  // g0 of the first round (floor)
         u32x4 G[4], Pg[4];
-#pragma unroll
+    #pragma unroll
         for (int q = 0; q < 4; ++q) {
             G[q] = gload(srsrc, gbase + q);
             if (TEMP) Pg[q] = gload(prsrc, gbase + q);
@@ -578,13 +459,7 @@ __device__ __forceinline__ void band4(const UnFrames& p, int fz, int NW, int wv,
         auto load_far = [&](NbVals& f, int x) {
             f.v[NB_B] = r == 0 && x >= 0 ? (int)lds[btop + (x & (kHand - 1))] : 0;
             f.v[NB_C] = r == 0 && x >= 1 ? (int)lds[btop + ((x - 1) & (kHand - 1))] : 0;
-            f.v[NB_AP] = lds[far(x, -T, 0)];
-            f.v[NB_BP] = lds[far(x, 0, -T)];
-            f.v[NB_CP] = lds[far(x, -T, -T)];
-            f.v[NB_AP1] = lds[far(x, -TT, 0)];
-            f.v[NB_BP1] = lds[far(x, 0, -TT)];
-            f.v[NB_ABP] = lds[far(x, -1, -T)];
-            f.v[NB_BAP] = lds[far(x, -T, -1)];
+            load_far_nbs(f, T, [&](int dx, int dy) { return (int)lds[far(x, dx, dy)]; });
         };
         if (b > 0) {  // the first two rounds' columns of the band above
             wait_ge((b - 1) * stride + min(kSync + 72, kend));
@@ -601,20 +476,15 @@ __device__ __forceinline__ void band4(const UnFrames& p, int fz, int NW, int wv,
                 // every store issued before the last round has completed: the
                 // pixels of steps < ks - 24 are in memory (a pixel of step s is
                 // stored by the round starting at <= s + 15)
-                if constexpr (XCU) {
-                    if constexpr (TEMP) asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
-                    else asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-                } else {
-                    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-                    __builtin_amdgcn_s_waitcnt(0);
-                }
+                if constexpr (TEMP) asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
+                else asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
                 if (r == 0) __hip_atomic_store(pos + wv, b * stride + ks - 24, __ATOMIC_RELAXED, kScope);
                 if (b > 0) {  // stored into the LDS ring at the end of this round
                     wait_ge((b - 1) * stride + min(ks + 2 * kSync + 72, kend));
                     hload(ks + kSync);
                 }
             }
-#pragma unroll
+    #pragma unroll
             for (int q = 0; q < kSync / 8; ++q) {
                 const int k0 = ks + 8 * q;
                 const int g0 = (k0 - r) >> 3;
@@ -622,12 +492,12 @@ __device__ __forceinline__ void band4(const UnFrames& p, int fz, int NW, int wv,
                 {   // group g0 - 1 is complete: LDS ring -> one 16-byte store
                     const int gs = g0 - 1;
                     const u32x4 ov4 = *(const u32x4*)(lds + ring_off + r * kRing + ((8 * gs) & (kRing - 1)));
-                    __builtin_amdgcn_raw_buffer_store_b128(ov4, orsrc, goff(gs), 0, XCU ? 16 /*sc1*/ : 0);
+                    __builtin_amdgcn_raw_buffer_store_b128(ov4, orsrc, goff(gs), 0, 16 /*sc1*/);
                 }
                 const u32x4 Ga = G[q & 3], Gb = G[(q + 1) & 3];
                 const u32x4 Pa = TEMP ? Pg[q & 3] : Ga, Pb = TEMP ? Pg[(q + 1) & 3] : Gb;
                 if (k0 < kend) {
-#pragma unroll
+    #pragma unroll
                     for (int j = 0; j < 8; ++j) {
                         const int k = k0 + j;
                         const int x = k - r;
@@ -649,8 +519,8 @@ __device__ __forceinline__ void band4(const UnFrames& p, int fz, int NW, int wv,
                         const int res = unsymbolize16(sv);
                         const int P = TEMP ? (int)pv : 0;
                         int val;
-                        if (k >= edge_k && y0 > 0) val = inv_tile3<FAM, K, TC_XY, TEMP>(g, res, P, u, v);
-                        else val = inv_edge3<FAM, K, TEMP>(g, res, P, u, v, tx, ty, k >= edge_k);
+                        if (k >= edge_k && y0 > 0) val = inv_tile<FAM, K, TC_XY, TEMP>(g, res, P, u, v);
+                        else val = inv_edge<FAM, K, TEMP>(g, res, P, u, v, tx, ty, k >= edge_k);
                         const uint16_t o16 = (uint16_t)val;
                         if (ok) {
                             lds[ring_off + r * kRing + (x & (kRing - 1))] = o16;
@@ -674,29 +544,11 @@ __device__ __forceinline__ void band4(const UnFrames& p, int fz, int NW, int wv,
             }
         }
         // every row's groups are stored: drain, then the band is complete
-        if constexpr (XCU) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        else {
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-            __builtin_amdgcn_s_waitcnt(0);
-        }
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         if (r == 0) __hip_atomic_store(pos + wv, b * stride + kend, __ATOMIC_RELAXED, kScope);
     }
 }
 
-// band5: the band pipeline spread over the whole chip -- one single-wave
-// workgroup per (band, frame).  HIP promises neither a dispatch order nor a
-// workgroup -> XCD placement, so a workgroup does not take its band from
-// blockIdx: its first act is to draw a ticket (an agent-scope atomic add on
-// the control block) and it decodes band ticket / nfr of frame ticket % nfr.
-// Tickets go out in the order the workgroups actually started, so the band a
-// workgroup waits for (ticket - nfr) belongs to a workgroup that is already
-// resident, and the chain of waits always ends at a running band 0, wherever
-// and whenever the workgroups were placed.  Progress words (one per band, 0
-// before the launch) live in the same hipMalloc'd control block: bands
-// publish with write-through (sc1) stores after draining their pixel stores
-// and poll with sc1 loads (MI355X_MICROARCH.md, visibility, write-through
-// form).  Config 3: 2048 waves over 256 CUs instead of 64 workgroups of 8
-// waves on 64 CUs.
 template <int FAM, int K>
 __global__ __launch_bounds__(64) void unpredict_band5(UnFrames p, int* ctl, int nbands, int nfr)
 {
@@ -708,8 +560,8 @@ __global__ __launch_bounds__(64) void unpredict_band5(UnFrames p, int* ctl, int 
     const int fz = p.first + fi * p.step;
     if (fz >= p.nz || b >= nbands) return;  // (the grid is exactly nbands * nfr)
     int* pos = ctl + kCtlPos + (size_t)fi * nbands;
-    if (p.video && ((p.z0 + fz) & 1)) band4<FAM, K, true, true>(p, fz, nbands, b, lds5, 0, 64 * kRing, pos);
-    else band4<FAM, K, false, true>(p, fz, nbands, b, lds5, 0, 64 * kRing, pos);
+    if (p.video && ((p.z0 + fz) & 1)) band5_body<FAM, K, true>(p, fz, nbands, b, lds5, 0, 64 * kRing, pos);
+    else band5_body<FAM, K, false>(p, fz, nbands, b, lds5, 0, 64 * kRing, pos);
 }
 
 template <int FAM, int K>
@@ -724,33 +576,28 @@ __global__ __launch_bounds__(64) void unpredict_band3(UnFrames p)
     else band3<FAM, K, false>(p, fz, ring, top);
 }
 
-template <int FAM, int K>
-__global__ __launch_bounds__(64) void unpredict_band2(UnFrames p)
-{
-    extern __shared__ __attribute__((aligned(16))) uint16_t lds2[];
-    const int fz = p.first + (int)blockIdx.x * p.step;
-    if (fz >= p.nz) return;
-    uint16_t* ring = lds2;
-    uint16_t* top = lds2 + 64 * kRing;
-    if (p.video && ((p.z0 + fz) & 1)) band2<FAM, K, true>(p, fz, ring, top);
-    else band2<FAM, K, false>(p, fz, ring, top);
-}
+// Which kernel decodes a W x H frame of lenslet size T (1 <= T <= 31).
+enum class UnPath { Chain, FrameWave, OneWave };
 
-static size_t band2_lds(const UnFrames& p) { return (size_t)(64 * kRing + (p.T + 1) * p.W) * sizeof(uint16_t); }
+// LDS of the frame wave: the band's ring and the `top` rows at full width
+static size_t frame_wave_lds(int W, int T) { return (size_t)(64 * kRing + (T + 1) * W) * sizeof(uint16_t); }
 
-static bool band2_ok(const UnFrames& p)
+static UnPath choose_path(int W, int H, int T)
 {
-    return p.T <= 30 && band2_lds(p) <= 160 * 1024;
-}
-
-// waves per frame for band4 (0: not applicable; rows are read and written in
-// aligned 8-column groups, so W is a multiple of 8)
-static int band4_waves(const UnFrames& p)
-{
-    // (band4 / band5 address a frame through 31-bit buffer offsets)
-    if (p.T < 2 || p.T > 30 || (p.W & 7) || (size_t)p.W * p.H * 2 >= 0x7FFFFFF0u) return 0;
-    const int nw = std::min(8, (p.H + 63) / 64);
-    return nw >= 2 ? nw : 0;
+    // the frame wave and the chain read a step's far neighbours one step
+    // early: nothing closer than two steps away may be among them
+    if (T < 2) return UnPath::OneWave;
+    // `top` / the hand-over ring are overwritten in place 64 - 2(T+1) steps
+    // after their last reader
+    if (T > 30) return UnPath::OneWave;
+    // the frame wave's `top` rows must fit a CU's 160 KiB of LDS.  (The
+    // chain does not use them, but has always been gated by them too, so a
+    // very wide frame goes to the one-wave kernel: kept as it is.)
+    if (frame_wave_lds(W, T) > 160 * 1024) return UnPath::OneWave;
+    // the chain moves rows in aligned 8-column groups, addresses a frame
+    // through 31-bit buffer offsets, and needs a second band to hand over to
+    if ((W & 7) == 0 && (size_t)W * H * 2 < 0x7FFFFFF0u && H > 64) return UnPath::Chain;
+    return UnPath::FrameWave;
 }
 
 // Hand-over limits.  LFM_UNPREDICT_WAIT_MS (default 500): a band5 wait
@@ -856,74 +703,68 @@ static void ctl_release(CtlBlock* c, hipStream_t st)
     c->busy = false;
 }
 
-template <int FAM, int K_>
-static hipError_t launch_band2(const UnFrames& p, int grid, hipStream_t st, int* ctl)
+template <int FAM, int K>
+static hipError_t launch_one_wave(const UnFrames& p, int grid, hipStream_t st)
 {
-    if (band4_waves(p)) {
-        const int nbands = (p.H + 63) / 64;
-        const size_t lds = (size_t)(64 * kRing + (p.T + 1) * kHand) * 2;
-        // ticket and progress words of this launch start at 0 (every wait
-        // needs a progress > 0); the status word accumulates over the call
-        hipError_t e = hipMemsetAsync(ctl + kCtlTicket, 0, (size_t)(1 + grid * nbands) * sizeof(int), st);
-        UnFrames pt = p;
-        pt.status = (unsigned*)ctl;
-        pt.err_bit = kStBand5;
-        pt.spin_limit = band5_spin_limit();
-        pt.repair = 0;
-        if (e == hipSuccess) {
-            hipLaunchKernelGGL((unpredict_band5<FAM, K_>), dim3(grid * nbands), dim3(64), lds, st, pt, ctl, nbands,
-                               grid);
-            e = hipGetLastError();
-        }
-        // re-run on the device, no host round trip: a band that gave up
-        // decoded from rows that were not ready, so when the status word
-        // carries kStBand5 every frame of the launch runs again through the
-        // one-wave kernel (a frame's bands are one wave's loop: nothing to
-        // wait for); otherwise its waves return at once.  (The round-5 re-run
-        // was band4 -- 512 threads and up to 129 KiB of LDS per frame -- whose
-        // launch waited up to 9 ms for CUs held by the other decode slot's
-        // bzip2 kernels even when it had nothing to do.)
-        if (e == hipSuccess && fallback_enabled()) {
-            UnFrames pr = p;
-            pr.status = (unsigned*)ctl;
-            pr.err_bit = 0;
-            pr.repair = 1;
-            hipLaunchKernelGGL((unpredict_band<FAM, K_>), dim3(grid), dim3(64), 0, st, pr);
-            e = hipGetLastError();
-        }
-        return e;
-    }
-    const size_t lds = band2_lds(p);
-    // band3 reads a step's far neighbours one step early: T >= 2
-    const bool v2 = p.T < 2;
-    const void* fn = v2 ? (const void*)unpredict_band2<FAM, K_> : (const void*)unpredict_band3<FAM, K_>;
-    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-        return hipErrorInvalidValue;
-    if (v2) hipLaunchKernelGGL((unpredict_band2<FAM, K_>), dim3(grid), dim3(64), lds, st, p);
-    else hipLaunchKernelGGL((unpredict_band3<FAM, K_>), dim3(grid), dim3(64), lds, st, p);
+    hipLaunchKernelGGL((unpredict_band<FAM, K>), dim3(grid), dim3(64), 0, st, p);
     return hipGetLastError();
 }
 
-template <int FAM>
-static hipError_t launch_unpredict(int k, const UnFrames& p, hipStream_t st, int* ctl)
+template <int FAM, int K>
+static hipError_t launch_frame_wave(const UnFrames& p, int grid, hipStream_t st)
+{
+    const size_t lds = frame_wave_lds(p.W, p.T);
+    if (hipFuncSetAttribute((const void*)unpredict_band3<FAM, K>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                            (int)lds) != hipSuccess)
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL((unpredict_band3<FAM, K>), dim3(grid), dim3(64), lds, st, p);
+    return hipGetLastError();
+}
+
+template <int FAM, int K>
+static hipError_t launch_chain(const UnFrames& p, int grid, hipStream_t st, int* ctl)
+{
+    const int nbands = (p.H + 63) / 64;
+    const size_t lds = (size_t)(64 * kRing + (p.T + 1) * kHand) * 2;
+    // ticket and progress words of this launch start at 0 (every wait
+    // needs a progress > 0); the status word accumulates over the call
+    hipError_t e = hipMemsetAsync(ctl + kCtlTicket, 0, (size_t)(1 + grid * nbands) * sizeof(int), st);
+    if (e != hipSuccess) return e;
+    UnFrames pt = p;
+    pt.status = (unsigned*)ctl;
+    pt.err_bit = kStBand5;
+    pt.spin_limit = band5_spin_limit();
+    pt.repair = 0;
+    hipLaunchKernelGGL((unpredict_band5<FAM, K>), dim3(grid * nbands), dim3(64), lds, st, pt, ctl, nbands, grid);
+    e = hipGetLastError();
+    // re-run on the device, no host round trip: a band that gave up decoded
+    // from rows that were not ready, so when the status word carries
+    // kStBand5 every frame of the launch runs again through the one-wave
+    // kernel (a frame's bands are one wave's loop: nothing to wait for);
+    // otherwise its waves return at once.  One wave and 8 KiB of LDS per
+    // frame: it is dispatched at once beside the other decode slot's bzip2
+    // kernels even when it has nothing to do.
+    if (e == hipSuccess && fallback_enabled()) {
+        UnFrames pr = p;
+        pr.status = (unsigned*)ctl;
+        pr.err_bit = 0;
+        pr.repair = 1;
+        e = launch_one_wave<FAM, K>(pr, grid, st);
+    }
+    return e;
+}
+
+template <int FAM, int K>
+static hipError_t launch_path(UnPath path, const UnFrames& p, hipStream_t st, int* ctl)
 {
     const int grid = (p.nz - p.first + p.step - 1) / p.step;
     if (grid <= 0) return hipSuccess;
-    if (band2_ok(p)) {
-        switch (k) {
-#define LFM_K(K_) case K_: return launch_band2<FAM, K_>(p, grid, st, ctl);
-        LFM_K(1) LFM_K(2) LFM_K(3) LFM_K(4) LFM_K(5) LFM_K(6) LFM_K(7)
-#undef LFM_K
-        default: return hipErrorInvalidValue;
-        }
+    switch (path) {
+    case UnPath::Chain: return launch_chain<FAM, K>(p, grid, st, ctl);
+    case UnPath::FrameWave: return launch_frame_wave<FAM, K>(p, grid, st);
+    case UnPath::OneWave: return launch_one_wave<FAM, K>(p, grid, st);
     }
-    switch (k) {
-#define LFM_K(K_) case K_: hipLaunchKernelGGL((unpredict_band<FAM, K_>), dim3(grid), dim3(64), 0, st, p); break;
-    LFM_K(1) LFM_K(2) LFM_K(3) LFM_K(4) LFM_K(5) LFM_K(6) LFM_K(7)
-#undef LFM_K
-    default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    return hipErrorInvalidValue;
 }
 
 // (checks that compile this file for one kernel define LFM_UNPREDICT_NO_ENTRY:
@@ -948,8 +789,9 @@ static int unpredict_issue(const uint16_t* d_sym, const uint16_t* d_prev, uint16
     if (any_temporal && family != 0) return LFM_HIP_ENOTINV;  // ((I - pred) + P) >> 1 drops a bit
     if (video && (z0 & 1) && !d_prev) return LFM_HIP_EINVAL;
     UnFrames p{d_sym, d_prev, d_out, W, H, T, nframes, z0, video, 0, 1, INT_MAX, 0u, nullptr, wait_ticks(), 0};
+    const UnPath path = choose_path(W, H, T);
     CtlBlock* ctl = nullptr;
-    if (band2_ok(p) && band4_waves(p)) {
+    if (path == UnPath::Chain) {  // ticket, progress and status words
         const int nbands = (H + 63) / 64;
         ctl = ctl_acquire((size_t)kCtlPos + (size_t)nframes * nbands);
         if (!ctl) return LFM_HIP_ERUNTIME;
@@ -971,10 +813,12 @@ static int unpredict_issue(const uint16_t* d_sym, const uint16_t* d_prev, uint16
         }
         hipError_t e = hipErrorInvalidValue;
         int* c = ctl ? ctl->d : nullptr;
-        switch (family) {
-        case 0: e = lfm::launch_unpredict<0>(predictor, p, st, c); break;
-        case 1: e = lfm::launch_unpredict<1>(predictor, p, st, c); break;
-        case 2: e = lfm::launch_unpredict<2>(predictor, p, st, c); break;
+        switch (family * 8 + predictor) {
+#define LFM_FK(F_, K_) case F_ * 8 + K_: e = launch_path<F_, K_>(path, p, st, c); break;
+#define LFM_F(F_) LFM_FK(F_, 1) LFM_FK(F_, 2) LFM_FK(F_, 3) LFM_FK(F_, 4) LFM_FK(F_, 5) LFM_FK(F_, 6) LFM_FK(F_, 7)
+        LFM_F(0) LFM_F(1) LFM_F(2)
+#undef LFM_F
+#undef LFM_FK
         }
         if (e != hipSuccess) rc = LFM_HIP_ERUNTIME;
     }
@@ -991,6 +835,12 @@ static int unpredict_issue(const uint16_t* d_sym, const uint16_t* d_prev, uint16
 } // namespace lfm
 
 #ifndef LFM_UNPREDICT_NO_ENTRY
+extern "C" int lfm_hip_unpredict_path(int W, int H, int T)
+{
+    if (W <= 0 || H <= 0 || T <= 0 || T > 31) return -1;
+    return (int)lfm::choose_path(W, H, T);
+}
+
 extern "C" int lfm_hip_unpredict_check(int status)
 {
     if (!status) return LFM_HIP_OK;

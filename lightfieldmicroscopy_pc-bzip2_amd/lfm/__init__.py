@@ -42,6 +42,7 @@ EXPORTS = [
     "lfm_decode_shard_plan", "lfm_decode_memory_multi", "lfm_decode_memory_multi_device",
     # lfm_hip.h
     "lfm_hip_predict", "lfm_hip_unpredict", "lfm_hip_unpredict_async", "lfm_hip_unpredict_check",
+    "lfm_hip_unpredict_path",
     "lfm_hip_predict_candidates", "lfm_hip_entropy2d", "lfm_hip_select_workspace_bytes", "lfm_hip_select",
     "lfm_hip_synth", "lfm_hip_device_count", "lfm_hip_force_generic", "lfm_hip_bzip2_workspace_bytes", "lfm_hip_bzip2_out_cap",
     "lfm_hip_bzip2_blocks", "lfm_hip_bzip2_last_stage_ms", "lfm_hip_bunzip2_workspace_bytes", "lfm_hip_bunzip2_blocks", "lfm_hip_scatter_blocks",
@@ -196,6 +197,8 @@ def lib():
                                                    ctypes.POINTER(DecodeStats)]
     if hasattr(L, "lfm_hip_crop_region"):
         L.lfm_hip_crop_region.argtypes = [vp, u32p, u32p, u32p, ctypes.c_uint32, vp, vp]
+    if hasattr(L, "lfm_hip_unpredict_path"):
+        L.lfm_hip_unpredict_path.argtypes = [ctypes.c_int] * 3
     # the multi-GPU reader, likewise
     intp = ctypes.POINTER(ctypes.c_int)
     if hasattr(L, "lfm_set_decode_devices"):
@@ -834,6 +837,15 @@ def unpredict_device(d_sym, d_out, W, H, nframes, T, family, predictor, video=0,
     rc = lib().lfm_hip_unpredict(p(d_sym), p(d_prev), p(d_out), W, H, nframes, T, FAMILIES.get(family, family),
                                  predictor, video, z0, _stream(stream))
     _check(rc, "lfm_hip_unpredict")
+
+
+UNPREDICT_PATHS = ("chain", "frame-wave", "one-wave")
+
+
+def unpredict_path(W, H, T):
+    """Which inverse-predictor kernel decodes W x H frames of lenslet size T: an
+    index into UNPREDICT_PATHS, or -1 for a shape the inverse rejects.  No GPU."""
+    return int(lib().lfm_hip_unpredict_path(W, H, T))
 
 
 def predict_candidates_device(d_frame, d_out7, W, H, T, family, stream=None):

@@ -1,5 +1,5 @@
 """Inverse-predictor timing by shape (decode critical path): one band, one
-frame, the config-3 stack; LFM_UNPREDICT_XCU selects band5 (default) / band4.
+frame, the config-3 stack; each line names the kernel path the shape took.
 python scripts/unpred_probe.py"""
 import json
 import os
@@ -30,4 +30,4 @@ for (X, Y, Z) in [(2048, 64, 1), (2048, 128, 1), (2048, 512, 1), (2048, 2048, 1)
     e1.record(st)
     torch.cuda.synchronize()
     print(json.dumps({"shape": [X, Y, Z], "ms": round(e0.elapsed_time(e1) / n, 4), "exact": bool(torch.equal(r, d)),
-                      "xcu": os.environ.get("LFM_UNPREDICT_XCU", "1")}), flush=True)
+                      "path": lfm.UNPREDICT_PATHS[lfm.unpredict_path(X, Y, T)]}), flush=True)

@@ -290,6 +290,25 @@ def test_family_switch(lfmlib):
         lfmlib.set_family(5)
 
 
+@pytest.mark.parametrize("W,H,T,path", [
+    (2048, 2048, 15, 0), (200, 150, 13, 0), (72, 90, 2, 0), (2048, 65, 15, 0),
+    (2504, 70, 30, 0),       # (4096 + 31 * 2504) * 2 = 163440 B <= 160 KiB of LDS
+    (16384, 65528, 2, 0),    # a frame just under the 31-bit buffer offset limit
+    (2048, 64, 15, 1),       # one band: nothing to hand over
+    (300, 130, 15, 1), (70, 90, 2, 1),  # W % 8
+    (45, 31, 5, 1), (1, 1, 13, 1),
+    (16384, 65536, 2, 1),    # W * H * 2 >= 0x7FFFFFF0
+    (64, 70, 31, 2),         # T == 31
+    (2560, 70, 30, 2),       # the LDS gate: 166912 B
+    (33, 70, 1, 2),          # T == 1
+    (8, 8, 0, -1), (8, 8, 32, -1)])
+def test_unpredict_path_choice(lfmlib, W, H, T, path):
+    """Which inverse-predictor kernel a shape takes (lfm_hip_unpredict_path: 0
+    the chain, 1 the frame wave, 2 the one-wave kernel, -1 rejected)."""
+    assert lfmlib.unpredict_path(W, H, T) == path
+    assert lfmlib.UNPREDICT_PATHS == ("chain", "frame-wave", "one-wave")
+
+
 def test_band5_release_wait_covers_the_round_stores():
     """The inverse predictor's band hand-over publishes progress after a
     hand-counted `s_waitcnt vmcnt(2)` (3 on temporal frames): compile
