@@ -166,6 +166,8 @@ def lib():
     L.lfm_decode_memory_roi.argtypes = [vp, ctypes.c_uint64, u32p, u32p, vp, ctypes.c_uint64, ctypes.c_int]
     L.lfm_hip_predict.argtypes = [vp, vp, vp] + [ctypes.c_int] * 8 + [vp]
     L.lfm_hip_unpredict.argtypes = [vp, vp, vp] + [ctypes.c_int] * 8 + [vp]
+    L.lfm_hip_unpredict_async.argtypes = [vp, vp, vp] + [ctypes.c_int] * 8 + [vp, vp]
+    L.lfm_hip_unpredict_check.argtypes = [ctypes.c_int]
     L.lfm_hip_predict_candidates.argtypes = [vp, vp] + [ctypes.c_int] * 4 + [vp]
     L.lfm_hip_entropy2d.argtypes = [vp, ctypes.c_uint64, f32p, vp]
     L.lfm_hip_bzip2_workspace_bytes.argtypes = [ctypes.c_uint32, ctypes.c_uint32]
@@ -837,6 +839,28 @@ def unpredict_device(d_sym, d_out, W, H, nframes, T, family, predictor, video=0,
     rc = lib().lfm_hip_unpredict(p(d_sym), p(d_prev), p(d_out), W, H, nframes, T, FAMILIES.get(family, family),
                                  predictor, video, z0, _stream(stream))
     _check(rc, "lfm_hip_unpredict")
+
+
+def unpredict_device_async(d_sym, d_out, W, H, nframes, T, family, predictor, video=0, z0=0, d_prev=None, status=None,
+                           stream=None):
+    """lfm_hip_unpredict_async: unpredict_device without the synchronisation.  The
+    kernels are queued on `stream` and the call's status word is copied behind
+    them into status[0] (`status`: a pinned int32 host tensor); once the stream
+    has passed that point the word goes to unpredict_check."""
+    if status is None or not status.is_pinned() or str(status.dtype) != "torch.int32" or status.numel() < 1:
+        raise ValueError("unpredict_device_async: status is a pinned int32 host tensor")
+    p = lambda t: None if t is None else (t.data_ptr() if hasattr(t, "data_ptr") else int(t))  # noqa: E731
+    rc = lib().lfm_hip_unpredict_async(p(d_sym), p(d_prev), p(d_out), W, H, nframes, T, FAMILIES.get(family, family),
+                                       predictor, video, z0, status.data_ptr(), _stream(stream))
+    _check(rc, "lfm_hip_unpredict_async")
+
+
+def unpredict_check(status):
+    """lfm_hip_unpredict_check on a status word of unpredict_device_async (the
+    tensor or its value): returns when the pixels are valid, a repaired band
+    hand-over timeout included (reported on stderr); raises otherwise."""
+    word = int(status.reshape(-1)[0]) if hasattr(status, "reshape") else int(status)
+    _check(lib().lfm_hip_unpredict_check(word), "lfm_hip_unpredict_check")
 
 
 UNPREDICT_PATHS = ("chain", "frame-wave", "one-wave")

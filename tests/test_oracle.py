@@ -106,6 +106,26 @@ def test_oracle_roundtrip_full_range(oracle):
         assert np.array_equal(oracle.unpredict_volume(s, 5, "tiles", k, 1), img)
 
 
+@pytest.mark.parametrize("W,H,T", [(8, 65, 2), (24, 70, 5), (72, 65, 2), (7, 65, 2), (1, 130, 2), (63, 129, 13),
+                                   (65, 66, 30), (64, 130, 1), (31, 31, 31), (62, 65, 31)])
+def test_unpredict_is_a_bijection_on_arbitrary_symbols(oracle, W, H, T):
+    """unpredict_volume of ARBITRARY uint16 symbols (not only of forward
+    symbols) is a valid reference: zig-zag is a bijection on uint16 and every
+    inverse formula is defined for any residual, so the forward pass of the
+    decoded frames returns the symbols.  An all-0xFFFF frame (residual -32768)
+    and an all-0xFFFE frame are among them; every family and predictor, video
+    for tiles.  (tests/test_unpredict_gpu.py compares the kernels with it.)"""
+    rng = np.random.default_rng(W * 1009 + H * 31 + T)
+    for k in range(1, 8):
+        sym = rng.integers(0, 65536, size=(3, H, W), dtype=np.uint16)
+        sym[k % 3] = 0xFFFF
+        sym[(k + 1) % 3] = 0xFFFE
+        for fam in ("tiles", "angle", "space"):
+            for video in ((0, 1) if fam == "tiles" else (0,)):
+                dec = oracle.unpredict_volume(sym, T, fam, k, video)
+                assert np.array_equal(oracle.predict_volume(dec, T, fam, k, video), sym), (fam, k, video)
+
+
 def test_symbolize_bijective(oracle):
     L = oracle.lib()
     import ctypes
