@@ -169,6 +169,24 @@ LFM_API int lfm_encoder_encode_multi(lfm_encoder* enc, const void* img, const ui
                                      const char metadata[KLB_METADATA_SIZE], const uint8_t** out, uint64_t* out_len,
                                      lfm_encode_stats* stats);
 
+/* GPU bzip2 of streams that libbzip2 cuts into several bzip2 blocks: blocks
+ * above about 900 kB (the level is capped at 9), or blocks whose data grows
+ * under bzip2's first run-length stage.  1 (the default; env
+ * LFM_BZ2_MULTIBLOCK=0 starts with 0): the device cuts, compresses and joins
+ * them.  0: such streams are compressed by the host library, as before this
+ * switch existed.  The .lfm bytes are the same either way.  The setter
+ * returns the previous value; it applies to encodes started after it. */
+LFM_API int lfm_set_bzip2_multiblock(int on);
+LFM_API int lfm_get_bzip2_multiblock(void);
+/* How the bzip2 streams (one per 5-D block) of the last encode were compressed
+ * that lfm_encoder_encode, lfm_encoder_encode_slab or lfm_encoder_wait
+ * completed on this encoder: all streams, those the host library compressed,
+ * and the bzip2 blocks the GPU produced (a stream may hold several).  Without
+ * a GPU host_streams == streams.  lfm_encoder_encode_multi encodes on other
+ * encoders: after it all three are 0.  Any pointer may be NULL. */
+LFM_API int lfm_encoder_stream_counts(lfm_encoder* enc, uint64_t* streams, uint64_t* host_streams,
+                                      uint64_t* bzip2_blocks);
+
 /* Free the device / pinned buffers the writers keep between calls. */
 LFM_API void lfm_release_encoders(void);
 

@@ -100,8 +100,30 @@ size_t lfm_hip_bzip2_out_cap(uint32_t block_bytes);
 int lfm_hip_bzip2_blocks(const void* d_img, const uint32_t dims[5], const uint32_t bs[5], uint32_t bpp,
                          uint32_t first, uint32_t count, uint32_t level, void* d_ws, size_t ws_bytes,
                          void* d_payload, uint64_t* h_sizes, uint32_t* h_flags, void* stream);
+/* The same for streams that libbzip2 cuts into several bzip2 blocks (RLE1 text
+ * reaching nblockMAX = 100000 * level - 19): the device finds the cuts as
+ * libbzip2 does, compresses every part as a block of its own and joins them
+ * at bit offsets behind one stream header, so only periodic streams (any
+ * periodic part) come back flagged.  A stream takes max_parts slots of the
+ * workspace, max_parts from the worst-case RLE1 length (5/4 of blockBytes) and
+ * nblockMAX(level), each slot sized for one block of that level.  Where
+ * max_parts is 1 (the default 96x96x8 uint16 block at its level 2) the size,
+ * the layout and the launches are those of lfm_hip_bzip2_blocks, and a stream
+ * that would need a second block is flagged.  Arguments, payload capacity,
+ * stage times and the stage hook as for lfm_hip_bzip2_blocks; the workspace is
+ * lfm_hip_bzip2_workspace_bytes_multi(count, blockBytes, level) (0 for a
+ * level outside 1..9).  lfm_hip_bzip2_max_count_multi: the largest count one
+ * call takes (the slots' texts are indexed in 32 bits). */
+size_t lfm_hip_bzip2_workspace_bytes_multi(uint32_t count, uint32_t block_bytes, uint32_t level);
+uint32_t lfm_hip_bzip2_max_count_multi(uint32_t block_bytes, uint32_t level);
+int lfm_hip_bzip2_blocks_multi(const void* d_img, const uint32_t dims[5], const uint32_t bs[5], uint32_t bpp,
+                               uint32_t first, uint32_t count, uint32_t level, void* d_ws, size_t ws_bytes,
+                               void* d_payload, uint64_t* h_sizes, uint32_t* h_flags, void* stream);
+/* bzip2 blocks in the payload of the calling thread's last lfm_hip_bzip2_blocks
+ * or lfm_hip_bzip2_blocks_multi (one per unflagged stream for the former). */
+uint64_t lfm_hip_bzip2_last_blocks(void);
 /* Stage times (HIP events on its stream, ms) of the calling thread's last
- * lfm_hip_bzip2_blocks: [0] RLE1 + CRC, [1] BWT (buckets, chunk sorts, tie
+ * lfm_hip_bzip2_blocks / lfm_hip_bzip2_blocks_multi: [0] RLE1 + CRC, [1] BWT (buckets, chunk sorts, tie
  * rounds), [2] MTF + RUNA/RUNB, [3] Huffman tables, [4] bit emission +
  * compaction.  Returns 0, or 3 when no call has completed on this thread. */
 int lfm_hip_bzip2_last_stage_ms(float ms[5]);

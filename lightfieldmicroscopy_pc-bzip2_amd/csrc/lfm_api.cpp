@@ -179,9 +179,23 @@ extern "C" int lfm_encoder_encode_multi(lfm_encoder* e, const void* img, const u
     lfm::MemSink sink(&e->enc.mem_out);
     int rc = lfm::encode_multi(img, h, sink, stats, e->threads, lfm::encode_devices());
     if (rc == -1) rc = e->enc.encode(img, false, h, sink, stats, e->threads);
+    e->enc.last_counts = {};
     *out = e->enc.mem_out.data();
     *out_len = e->enc.mem_out.size();
     return rc;
+}
+
+extern "C" int lfm_set_bzip2_multiblock(int on) { return lfm::set_bzip2_multiblock(on); }
+extern "C" int lfm_get_bzip2_multiblock(void) { return lfm::bzip2_multiblock(); }
+
+extern "C" int lfm_encoder_stream_counts(lfm_encoder* e, uint64_t* streams, uint64_t* host_streams,
+                                         uint64_t* bzip2_blocks)
+{
+    if (!e) return 3;
+    if (streams) *streams = e->enc.last_counts.streams;
+    if (host_streams) *host_streams = e->enc.last_counts.host_streams;
+    if (bzip2_blocks) *bzip2_blocks = e->enc.last_counts.bzip2_blocks;
+    return 0;
 }
 
 extern "C" void lfm_release_encoders(void) { lfm::release_pooled_encoders(); }

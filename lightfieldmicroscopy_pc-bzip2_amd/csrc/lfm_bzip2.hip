@@ -35,9 +35,19 @@
 //           written by all threads at prefix-summed bit offsets; the streams
 //           are then compacted into the payload.
 //
-// Streams whose RLE1 block reaches nblockMAX (libbzip2 would cut a second
-// block) or that are periodic are flagged for the host library: the output
-// stays byte-identical in every case.
+// A stream whose RLE1 text reaches nblockMAX = 100000 * level - 19 is several
+// bzip2 blocks in libbzip2 (every block above ~900 kB; smaller ones whose data
+// grows under RLE1).  lfm_hip_bzip2_blocks_multi gives a stream max_parts
+// slots of the batch, one per bzip2 block ("part"): rle1_crc<.., MULTI> writes
+// the text uncut, finds the cuts as libbzip2 does and the parts' CRCs,
+// place_parts copies every part's text into its slot, BWT / MTF / Huffman run
+// per slot as they do per stream, emit_stream<MULTI> writes a slot by role
+// (stream header in the first only, no trailer) and join_parts concatenates
+// the parts at bit offsets and adds the end magic and the combined CRC.  With
+// max_parts == 1 it is lfm_hip_bzip2_blocks: one slot per stream, a stream
+// that would need a second block flagged for the host library.  Periodic
+// streams (any periodic part) are flagged too: the output stays
+// byte-identical in every case.
 #include <hip/hip_runtime.h>
 #include <rocprim/block/block_exchange.hpp>
 #include <rocprim/block/block_sort.hpp>
@@ -136,6 +146,24 @@ struct Batch {
     uint32_t* sfin;          // the final order of every rotation (bwt_place_sorted / bwt_induce)
     uint2* ent;              // bwt_induce's entries per final position (the keys_a area, free after the sorts)
     uint32_t it_full;        // sort every rotation (no induction): the fallback for ties that need doubling
+    // streams of several bzip2 blocks (lfm_hip_bzip2_blocks_multi): a stream
+    // owns `parts` consecutive slots, one per bzip2 block ("part") libbzip2
+    // would cut; every per-stream buffer above is then per slot (nstreams
+    // slots) except raw / raw_len, which stay per stream.  parts == 1: a
+    // stream is its slot and none of the fields below is used.
+    uint32_t parts;
+    uint32_t full_cap;       // bytes reserved per stream for the uncut RLE1 text
+    uint8_t* Tfull;          // uncut RLE1 texts (rle1_crc), copied into the slots by place_parts
+    uint32_t* part_toff;     // per slot: the part's offset in its stream's RLE1 text (its length: n)
+    uint32_t* part_roff;     // per slot: the part's offset and length in the raw block
+    uint32_t* part_rlen;
+    uint32_t* out_bits;      // per slot: bits emit_stream wrote (stream header / block, no trailer)
+    uint32_t* nparts;        // per stream: parts in use
+    uint32_t* sflags;        // per stream: kFlagHost
+    uint32_t* sbytes;        // per stream: bytes of the joined stream
+    uint32_t* jwords;        // per stream: the joined stream, jcap bytes, MSB-first bit words
+    uint32_t jcap;
+    uint32_t pay_cap;        // bytes the payload reserves per stream: a longer joined stream goes to the host
 };
 
 // ------------------------------------------------------------- gather --
@@ -280,7 +308,45 @@ __device__ __forceinline__ uint32_t chunk_byte(const uint32_t (&w)[kRleChunk / 4
     return (x >> (8 * (i & 3u))) & 255u;
 }
 
-template <bool FROM_IMG>
+// CRC register arithmetic for the part CRCs: the register is a polynomial
+// over GF(2) mod 0x104c11db7 (bit k = x^k) and a zero byte fed is a
+// multiplication by x^8, so Z^m(v) = v * x^(8 m).
+__device__ inline uint32_t crc_mul(uint32_t a, uint32_t b)
+{
+    uint32_t r = 0;
+#pragma unroll 1
+    for (int i = 31; i >= 0; --i) {
+        r = (r << 1) ^ ((r >> 31) ? 0x04c11db7u : 0u);
+        r ^= ((b >> i) & 1u) ? a : 0u;
+    }
+    return r;
+}
+
+__device__ inline uint32_t crc_xpow8(uint32_t m)  // x^(8 m)
+{
+    uint32_t r = 1u, b = 2u;
+#pragma unroll 1
+    for (uint64_t e = 8ull * m; e; e >>= 1) {
+        if (e & 1u) r = crc_mul(r, b);
+        b = crc_mul(b, b);
+    }
+    return r;
+}
+
+// MULTI (Batch::parts > 1): the text goes to Tfull uncut and the kernel finds
+// the stream's parts as libbzip2 cuts them (bzlib.c copy_input_until_stop,
+// handle_compress).  RLE1 works in pieces (a run of equal bytes, cut every 255)
+// flushed into the block when the next input byte arrives, and nblock >=
+// nblockMAX is tested before each input byte: a block ends in front of the
+// first piece whose text position has reached nblockMAX past the block's start
+// -- unless that piece is the stream's last byte, which libbzip2 has already
+// read when it looks (it joins the block).  The run state survives a cut, so
+// the parts' texts are consecutive ranges of the uncut text.  A tile holds
+// less text than a block, so at most one cut falls in it.  The CRC register
+// P(r) at a cut r comes from the chunk CRCs in front of it; a part [a, b)
+// then has CRC ~(P(b) ^ Z^(b-a)(P(a) ^ ~0)) (the register is affine in its
+// start value).
+template <bool FROM_IMG, bool MULTI>
 __global__ __launch_bounds__(kRleThreads) __attribute__((amdgpu_waves_per_eu(4))) void rle1_crc(Batch B)
 {
     constexpr uint32_t NW = kRleThreads / 64;
@@ -294,6 +360,7 @@ __global__ __launch_bounds__(kRleThreads) __attribute__((amdgpu_waves_per_eu(4))
     __shared__ uint32_t wcnt[NW], wcrc[NW];
     __shared__ RunSum s_carry;
     __shared__ uint32_t s_wr, s_crc;
+    __shared__ uint32_t s_ps, s_np, s_cut_r, s_cut_tp, s_red[NW];  // MULTI: the open part's text start and index, a tile's cut
     const uint32_t s = blockIdx.x, t = threadIdx.x, lane = t & 63, wave = t >> 6;
     uint32_t org[5], sz[5];
     block_box(B.g, B.first_block + s, org, sz);
@@ -339,9 +406,12 @@ __global__ __launch_bounds__(kRleThreads) __attribute__((amdgpu_waves_per_eu(4))
         s_carry = RunSum{0, 0, 0, 0, 0};
         s_wr = 0;
         s_crc = 0;
+        s_ps = 0;
+        s_np = 0;
+        s_cut_r = ~0u;
     }
-    uint8_t* Tout = B.T + (size_t)s * B.cap;
-    const uint32_t wlim = B.cap - 8;  // RLE1 bytes past this are not stored (the stream goes to the host)
+    uint8_t* Tout = MULTI ? B.Tfull + (size_t)s * B.full_cap : B.T + (size_t)s * B.cap;
+    const uint32_t wlim = (MULTI ? B.full_cap : B.cap) - 8;  // RLE1 bytes past this are not stored (the stream goes to the host)
     // this thread's 32 bytes of a tile; the next tile's are loaded while this
     // one is processed
     // (unconditional loads at clamped offsets: a load under a branch makes the
@@ -383,6 +453,7 @@ __global__ __launch_bounds__(kRleThreads) __attribute__((amdgpu_waves_per_eu(4))
             const uint32_t x = cc ^ __builtin_bswap32(w[q]);
             cc = crc4[3][x >> 24] ^ crc4[2][(x >> 16) & 255u] ^ crc4[1][(x >> 8) & 255u] ^ crc4[0][x & 255u];
         }
+        const uint32_t cc0 = cc;  // (MULTI: the register at a cut)
         // chunk run summary from the equal-neighbour mask
         const uint32_t Ein = chunk_eq_mask(w, nv);
         const uint32_t b0 = w[0] & 255u;
@@ -470,6 +541,46 @@ __global__ __launch_bounds__(kRleThreads) __attribute__((amdgpu_waves_per_eu(4))
             if (w2 < wave) base += wcnt[w2];
             total += wcnt[w2];
         }
+        // MULTI: the first piece start of the chunk at or past the open part's limit
+        uint32_t hit_tp = 0;
+        if (MULTI) {
+            const uint32_t thr = s_ps + B.nblock_max;
+            const uint32_t tpos = (wr0 & ~15u) + base;  // text position of the chunk's first output byte
+            uint32_t hit = ~0u;
+            if (nv && tpos + cnt > thr) {
+                if (!slow) {
+                    uint32_t sm = S;
+                    while (sm) {
+                        const uint32_t i = (uint32_t)__builtin_ctz(sm);
+                        sm &= sm - 1u;
+                        const uint32_t lt = (1u << i) - 1u;
+                        const uint32_t p = tpos + (uint32_t)__popc(omask & lt) + (uint32_t)__popc(cmask & (lt | (1u << i)));
+                        if (p >= thr) {
+                            hit = i;
+                            hit_tp = p;
+                            break;
+                        }
+                    }
+                } else {
+                    uint32_t ch = ch0, r = rl0, q = tpos;
+                    for (uint32_t i = 0; i < nv; ++i) {
+                        const uint32_t c = chunk_byte(w, i);
+                        const bool same = c == ch && r < 255;
+                        if (!same) {
+                            q += r >= 4 ? 1u : 0u;
+                            if (q >= thr && hit == ~0u) {
+                                hit = i;
+                                hit_tp = q;
+                            }
+                        }
+                        r = same ? r + 1 : 1u;
+                        ch = c;
+                        q += r <= 4 ? 1u : 0u;
+                    }
+                }
+            }
+            if (hit != ~0u) atomicMin(&s_cut_r, g + hit);
+        }
         if (!slow) {
             // copies in order, the count bytes after (each a few per chunk at most)
             uint32_t pos = base;
@@ -522,6 +633,39 @@ __global__ __launch_bounds__(kRleThreads) __attribute__((amdgpu_waves_per_eu(4))
             ncrc = crc_shift_b(crcsh[9], s_crc) ^ x;
         }
         __syncthreads();
+        if (MULTI) {
+            const uint32_t cr = s_cut_r;
+            if (cr != ~0u && cr != L - 1) {  // (every thread sees the same cr)
+                // P(cr): the stream register shifted over the tile's bytes in
+                // front of the cut, the whole chunks there shifted likewise,
+                // and the cut chunk's bytes before the cut
+                uint32_t x = 0;
+                if (nv && g + kRleChunk <= cr) {
+                    x = crc_mul(cc0, crc_xpow8(cr - g - kRleChunk));
+                } else if (nv && g <= cr) {
+                    x = g == 0 ? 0xffffffffu : 0u;
+                    for (uint32_t i = 0; i < cr - g; ++i) x = (x << 8) ^ crc4[0][(x >> 24) ^ chunk_byte(w, i)];
+                    s_cut_tp = hit_tp;
+                }
+                if (t == 0) x ^= crc_mul(s_crc, crc_xpow8(cr - tb));
+#pragma unroll
+                for (int d = 32; d; d >>= 1) x ^= __shfl_xor(x, d);
+                if (lane == 0) s_red[wave] = x;
+                __syncthreads();
+                if (t == 0) {
+                    uint32_t P = 0;
+                    for (uint32_t w2 = 0; w2 < NW; ++w2) P ^= s_red[w2];
+                    const uint32_t k = s_np + 1, slot = s * B.parts + k;
+                    if (k < B.parts) {  // (more parts than slots: the stream goes to the host)
+                        B.part_toff[slot] = s_cut_tp;
+                        B.part_roff[slot] = cr;
+                        B.crc[slot] = P;
+                    }
+                    s_np = k;
+                    s_ps = s_cut_tp;
+                }
+            }
+        }
         // whole 16-byte units out (16-byte stores; a unit starting before
         // wlim ends inside the 256-aligned cap), the last partial unit kept
         {
@@ -536,6 +680,7 @@ __global__ __launch_bounds__(kRleThreads) __attribute__((amdgpu_waves_per_eu(4))
             s_carry = ncarry;
             s_crc = ncrc;
             s_wr = wr0 + total;
+            if (MULTI) s_cut_r = ~0u;
         }
     }
     __syncthreads();
@@ -549,16 +694,68 @@ __global__ __launch_bounds__(kRleThreads) __attribute__((amdgpu_waves_per_eu(4))
         const uint32_t pad = (L + kRleTile - 1) / kRleTile * kRleTile - L;
         for (int j = 0; j < kCrcUnshift; ++j)
             if ((pad >> j) & 1u) crc = gf2_apply(c_crc_unshift[j], crc);
-        const bool host = total >= B.nblock_max || total > wlim;
-        B.crc[s] = L ? ~crc : 0u;
-        B.n[s] = total;
-        B.flags[s] = host ? kFlagHost : 0u;
-        B.done[s] = host ? 1u : 0u;
-        B.seg_begin[s] = s * B.cap;
-        B.seg_end[s] = s * B.cap + (host ? 0u : total);
+        if (!MULTI) {
+            const bool host = total >= B.nblock_max || total > wlim;
+            B.crc[s] = L ? ~crc : 0u;
+            B.n[s] = total;
+            B.flags[s] = host ? kFlagHost : 0u;
+            B.done[s] = host ? 1u : 0u;
+            B.seg_begin[s] = s * B.cap;
+            B.seg_end[s] = s * B.cap + (host ? 0u : total);
+        } else {
+            // the parts into their slots: offsets, lengths and CRCs (B.crc of
+            // the slots past the first holds P at their cut until here); the
+            // slots not in use are skipped like host streams
+            const uint32_t np = s_np + 1, s0 = s * B.parts;
+            bool host = np > B.parts || total > wlim;
+            for (uint32_t k = 0; k < np && !host; ++k) {
+                const uint32_t a = k ? B.part_toff[s0 + k] : 0u, b = k + 1 < np ? B.part_toff[s0 + k + 1] : total;
+                host = b - a > B.cap - 8;
+            }
+            for (uint32_t k = 0; k < B.parts; ++k) {
+                const uint32_t slot = s0 + k;
+                const bool used = !host && k < np;
+                uint32_t n = 0;
+                if (used) {
+                    const bool last = k + 1 == np;
+                    const uint32_t ta = k ? B.part_toff[slot] : 0u, tb2 = last ? total : B.part_toff[slot + 1];
+                    const uint32_t ra = k ? B.part_roff[slot] : 0u, rb = last ? L : B.part_roff[slot + 1];
+                    const uint32_t Pa = k ? B.crc[slot] : 0xffffffffu, Pb = last ? crc : B.crc[slot + 1];
+                    n = tb2 - ta;
+                    B.part_toff[slot] = ta;
+                    B.part_roff[slot] = ra;
+                    B.part_rlen[slot] = rb - ra;
+                    B.crc[slot] = ~(Pb ^ crc_mul(Pa ^ 0xffffffffu, crc_xpow8(rb - ra)));
+                }
+                B.n[slot] = n;
+                B.flags[slot] = used ? 0u : kFlagHost;
+                B.done[slot] = used ? 0u : 1u;
+                B.seg_begin[slot] = slot * B.cap;
+                B.seg_end[slot] = slot * B.cap + n;
+            }
+            B.nparts[s] = host ? 0u : np;
+            B.sflags[s] = host ? kFlagHost : 0u;
+        }
     }
     // the byte map of the RLE1 text comes from bwt_bucket's histogram
-    if (t < 8) B.inuse[s * 8 + t] = 0u;
+    for (uint32_t i = t; i < 8 * (MULTI ? B.parts : 1u); i += kRleThreads) B.inuse[s * (MULTI ? B.parts : 1u) * 8 + i] = 0u;
+}
+
+// MULTI: every part's text from the stream's uncut text into its slot
+// (dword stores; the source starts at any byte)
+__global__ __launch_bounds__(256) void place_parts(Batch B)
+{
+    const uint32_t slot = blockIdx.y;
+    if (B.flags[slot] & kFlagHost) return;
+    const uint32_t n = B.n[slot];
+    const uint8_t* src = B.Tfull + (size_t)(slot / B.parts) * B.full_cap + B.part_toff[slot];
+    uint32_t* dst = (uint32_t*)(B.T + (size_t)slot * B.cap);
+    for (uint32_t i = blockIdx.x * 256 + threadIdx.x; 4 * i < n; i += gridDim.x * 256) {
+        uint32_t v = 0;
+#pragma unroll
+        for (uint32_t b = 0; b < 4; ++b) v |= 4 * i + b < n ? (uint32_t)src[4 * i + b] << (8 * b) : 0u;
+        dst[i] = v;
+    }
 }
 
 // ------------------------------------------------------------------ BWT --
@@ -2962,6 +3159,10 @@ __device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t* wsum, 
 constexpr uint32_t kEmitC = 16;  // symbols per thread and round
 constexpr uint32_t kEmitBufWords = (kEmitThreads * kEmitC * 17 + 31) / 32 + 2;  // code lengths <= 17 bits
 
+// MULTI (Batch::parts > 1): a slot emits its part by role -- the stream header
+// only in a stream's first slot, then the block from its magic through its
+// last symbol, the exact bit count in out_bits; join_parts adds the trailer.
+template <bool MULTI>
 __global__ __launch_bounds__(kEmitThreads) void emit_stream(Batch B)
 {
     __shared__ uint32_t wsum[kEmitThreads / 64];
@@ -2972,7 +3173,7 @@ __global__ __launch_bounds__(kEmitThreads) void emit_stream(Batch B)
     __shared__ uint8_t sel_l[kSelLds];
     const uint32_t s = blockIdx.x, t = threadIdx.x;
     if (B.flags[s] & kFlagHost) {
-        if (t == 0) B.out_bytes[s] = 0;
+        if (t == 0) (MULTI ? B.out_bits : B.out_bytes)[s] = 0;
         return;
     }
     uint32_t* words = B.words + (size_t)s * (B.out_cap / 4);
@@ -3007,7 +3208,9 @@ __global__ __launch_bounds__(kEmitThreads) void emit_stream(Batch B)
             put_bits_hdr(hdr, words, p, nb, v);
             p += nb;
         };
-        put(8, 'B'); put(8, 'Z'); put(8, 'h'); put(8, '0' + B.level);
+        if (!MULTI || s % B.parts == 0) {
+            put(8, 'B'); put(8, 'Z'); put(8, 'h'); put(8, '0' + B.level);
+        }
         put(8, 0x31); put(8, 0x41); put(8, 0x59); put(8, 0x26); put(8, 0x53); put(8, 0x59);
         put(32, B.crc[s]);
         put(1, 0);
@@ -3169,6 +3372,10 @@ __global__ __launch_bounds__(kEmitThreads) void emit_stream(Batch B)
         words[data_end >> 5] = (data_end & 31) ? obuf[0] : 0u;
         for (uint64_t w = (data_end >> 5) + 1; w <= ((data_end + 80) >> 5) + 1; ++w) words[w] = 0;
     }
+    if (MULTI) {
+        if (t == 0) B.out_bits[s] = (uint32_t)data_end;
+        return;
+    }
     if (t == 0) {
         uint64_t p = data_end;
         auto put = [&](uint32_t nb2, uint32_t v) {
@@ -3178,6 +3385,63 @@ __global__ __launch_bounds__(kEmitThreads) void emit_stream(Batch B)
         put(8, 0x17); put(8, 0x72); put(8, 0x45); put(8, 0x38); put(8, 0x50); put(8, 0x90);
         put(32, B.crc[s]);  // combined CRC of a one-block stream: rotl(0, 1) ^ blockCRC
         B.out_bytes[s] = (uint32_t)((p + 7) >> 3);
+    }
+}
+
+// MULTI: a stream's parts joined at bit offsets into its jwords row, then the
+// end magic and the combined CRC (rotl(combined, 1) ^ blockCRC over the
+// parts).  One workgroup per stream, part after part: destination word i of a
+// part is a funnel shift of its source words i - 1 and i, and the word on a
+// part boundary also keeps the previous part's last bits.  A stream with a
+// periodic part (flagged by the BWT) goes to the host as a whole.
+__global__ __launch_bounds__(256) void join_parts(Batch B)
+{
+    const uint32_t s = blockIdx.x, t = threadIdx.x, s0 = s * B.parts;
+    const uint32_t np = B.nparts[s];
+    uint32_t host = B.sflags[s];
+    for (uint32_t k = 0; k < np; ++k) host |= B.flags[s0 + k] & kFlagHost;
+    if (host) {
+        if (t == 0) {
+            B.sflags[s] = kFlagHost;
+            B.sbytes[s] = 0;
+        }
+        return;
+    }
+    uint32_t* dst = B.jwords + (size_t)s * (B.jcap / 4);
+    uint64_t D = 0;
+    uint32_t comb = 0;
+    for (uint32_t k = 0; k < np; ++k) {
+        const uint32_t bits = B.out_bits[s0 + k], nsw = (bits + 31) >> 5;
+        const uint32_t* src = B.words + (size_t)(s0 + k) * (B.out_cap / 4);
+        const uint32_t sh = (uint32_t)(D & 31), ndw = (sh + bits + 31) >> 5;
+        const uint64_t wd0 = D >> 5;
+        auto sw = [&](uint32_t j) -> uint32_t {  // source word j, zero past the part's last bit
+            if (j >= nsw) return 0u;
+            const uint32_t v = src[j];
+            return (j == nsw - 1 && (bits & 31)) ? v & (~0u << (32 - (bits & 31))) : v;
+        };
+        for (uint32_t i = t; i < ndw; i += 256) {
+            uint32_t v = sw(i) >> sh;
+            if (sh && i) v |= sw(i - 1) << (32 - sh);
+            if (sh && !i) v |= dst[wd0];
+            dst[wd0 + i] = v;
+        }
+        __syncthreads();
+        D += bits;
+        comb = ((comb << 1) | (comb >> 31)) ^ B.crc[s0 + k];
+    }
+    if (t == 0) {
+        for (uint64_t w = (D + 31) >> 5; w <= ((D + 80) >> 5) + 1; ++w) dst[w] = 0;
+        uint64_t p = D;
+        auto put = [&](uint32_t nb2, uint32_t v) {
+            put_bits_atomic(dst, p, nb2, v);
+            p += nb2;
+        };
+        put(8, 0x17); put(8, 0x72); put(8, 0x45); put(8, 0x38); put(8, 0x50); put(8, 0x90);
+        put(32, comb);
+        const uint32_t nbytes = (uint32_t)((p + 7) >> 3);
+        B.sbytes[s] = nbytes <= B.pay_cap ? nbytes : 0u;
+        if (nbytes > B.pay_cap) B.sflags[s] = kFlagHost;
     }
 }
 
@@ -3355,6 +3619,7 @@ struct StageEvents {
 thread_local StageEvents t_stage;
 thread_local void (*t_hook)(void*, int) = nullptr;
 thread_local void* t_hook_ctx = nullptr;
+thread_local uint64_t t_last_blocks = 0;  // bzip2 blocks the calling thread's last call produced (lfm_hip_bzip2_last_blocks)
 
 // rocPRIM temporary storage for the largest use of each primitive in a batch
 // of `count` streams (size queries only: no device work).  Carved out of the
@@ -3409,17 +3674,44 @@ struct BwtStats {
     uint32_t left_runs = 0;   // runs tie_runs_direct left
 };
 
+// bzip2 blocks libbzip2 can cut a block of block_bytes into at `level`: the
+// RLE1 text is at most 5/4 of the block, and every part but the last holds at
+// least nblockMAX bytes of it
+uint32_t max_parts(uint32_t block_bytes, uint32_t level)
+{
+    const uint64_t worst = (uint64_t)block_bytes + block_bytes / 4 + 1;
+    return (uint32_t)(worst / (100000u * level - 19u)) + 1u;
+}
+
 // The workspace, described once: every buffer in order, 256-byte aligned.
 // With base == nullptr this only sums (lfm_hip_bzip2_workspace_bytes); with
 // the workspace base it also points B and S into it.  Either way it sets the
 // capacities of B the sizes derive from.  Returns the bytes needed.
-size_t layout(uint8_t* base, uint32_t count, uint32_t block_bytes, Batch& B, Scratch& S)
+//
+// level == 0: one slot per stream, sized for the whole block (the layout
+// lfm_hip_bzip2_workspace_bytes has always described).  level >= 1: the
+// stream owns max_parts(block_bytes, level) slots, each sized for one bzip2
+// block of that level; with one part that is the same layout, byte for byte.
+size_t layout(uint8_t* base, uint32_t streams, uint32_t block_bytes, uint32_t level, Batch& B, Scratch& S)
 {
+    B.parts = level ? max_parts(block_bytes, level) : 1u;
+    const uint32_t count = streams * B.parts;  // slots
     B.nstreams = count;
     B.raw_cap = (uint32_t)align_up(block_bytes, 16);  // stream stride of the raw blocks (16-byte loads)
     B.cap = rle_cap(block_bytes);
     B.out_cap = out_cap(block_bytes);
     B.sel_cap = sel_cap(block_bytes);
+    B.full_cap = B.cap;
+    if (B.parts > 1) {
+        // a part's text is at most nblockMAX + 5 bytes: the slack rle_cap adds
+        // for the 16-byte loads, the same alignment
+        const uint32_t part_max = 100000u * level - 19u + 5u;
+        B.cap = std::min(B.cap, (uint32_t)align_up((size_t)part_max + 64, 256));
+        B.out_cap = std::min(B.out_cap, out_cap(part_max));
+        B.sel_cap = (uint32_t)align_up(B.cap / kGSize + 8, 64);
+    }
+    B.jcap = B.parts * B.out_cap;
+    B.pay_cap = out_cap(block_bytes);
     const size_t n = count, N = n * B.cap;
     size_t off = 0;
     auto take = [&](auto*& p, size_t bytes) {
@@ -3427,7 +3719,7 @@ size_t layout(uint8_t* base, uint32_t count, uint32_t block_bytes, Batch& B, Scr
         p = base ? (P)(base + off) : nullptr;
         off += align_up(bytes, 256);
     };
-    take(B.raw, n * B.raw_cap);
+    take(B.raw, (size_t)streams * B.raw_cap);
     take(B.T, N);
     take(B.keys_a, N * 8);
     take(B.keys_b, N * 8);
@@ -3462,6 +3754,14 @@ size_t layout(uint8_t* base, uint32_t count, uint32_t block_bytes, Batch& B, Scr
     B.wide_cnt = base ? S.cnt + 3 : nullptr;
     S.tmp_bytes = prim_tmp_bytes(count, B.cap);
     take(S.tmp, S.tmp_bytes);
+    if (B.parts > 1) {
+        take(B.Tfull, (size_t)streams * B.full_cap);
+        uint32_t** per_slot[] = {&B.part_toff, &B.part_roff, &B.part_rlen, &B.out_bits};
+        for (uint32_t** q : per_slot) take(*q, n * 4 + 64);
+        uint32_t** per_stream[] = {&B.nparts, &B.sflags, &B.sbytes};
+        for (uint32_t** q : per_stream) take(*q, (size_t)streams * 4 + 64);
+        take(B.jwords, (size_t)streams * B.jcap);
+    }
     return off;
 }
 
@@ -3686,7 +3986,24 @@ extern "C" size_t lfm_hip_bzip2_workspace_bytes(uint32_t nstreams, uint32_t bloc
 {
     Batch B{};
     Scratch S{};
-    return layout(nullptr, nstreams, block_bytes, B, S);
+    return layout(nullptr, nstreams, block_bytes, 0, B, S);
+}
+
+extern "C" size_t lfm_hip_bzip2_workspace_bytes_multi(uint32_t nstreams, uint32_t block_bytes, uint32_t level)
+{
+    if (level < 1 || level > 9) return 0;
+    Batch B{};
+    Scratch S{};
+    return layout(nullptr, nstreams, block_bytes, level, B, S);
+}
+
+extern "C" uint32_t lfm_hip_bzip2_max_count_multi(uint32_t block_bytes, uint32_t level)
+{
+    if (level < 1 || level > 9) return 0;
+    Batch B{};
+    Scratch S{};
+    (void)layout(nullptr, 0, block_bytes, level, B, S);
+    return (uint32_t)(((1ull << 32) - 1) / ((uint64_t)B.parts * B.cap));
 }
 
 extern "C" size_t lfm_hip_bzip2_out_cap(uint32_t block_bytes) { return out_cap(block_bytes); }
@@ -3695,10 +4012,13 @@ extern "C" size_t lfm_hip_bzip2_out_cap(uint32_t block_bytes) { return out_cap(b
 // (device, image layout) into `payload` (device, contiguous in block order);
 // sizes[i] = compressed size of stream i, flags[i] != 0 -> the stream must be
 // produced by the host library (its bytes are absent from the payload).
-extern "C" int lfm_hip_bzip2_blocks(const void* d_img, const uint32_t dims[5], const uint32_t bs[5], uint32_t bpp,
-                                    uint32_t first, uint32_t count, uint32_t level, void* d_ws, size_t ws_bytes,
-                                    void* d_payload, uint64_t* h_sizes, uint32_t* h_flags, void* stream_)
+namespace {
+// multi: a stream may take several slots (layout with the level)
+int bzip2_blocks(const void* d_img, const uint32_t dims[5], const uint32_t bs[5], uint32_t bpp, uint32_t first,
+                 const uint32_t streams, uint32_t level, void* d_ws, size_t ws_bytes, void* d_payload,
+                 uint64_t* h_sizes, uint32_t* h_flags, void* stream_, bool multi)
 {
+    uint32_t count = streams;  // slots, once the layout is known
     hipStream_t st = (hipStream_t)stream_;
     if (!d_img || !dims || !bs || !bpp || !count || level < 1 || level > 9 || !d_ws || !d_payload) return LFM_HIP_EINVAL;
     int dev = 0;
@@ -3724,8 +4044,10 @@ extern "C" int lfm_hip_bzip2_blocks(const void* d_img, const uint32_t dims[5], c
     B.level = level;
     B.nblock_max = 100000u * level - 19u;
     Scratch S{};
-    if (ws_bytes < layout((uint8_t*)d_ws, count, raw_cap, B, S)) return LFM_HIP_EINVAL;
+    if (ws_bytes < layout((uint8_t*)d_ws, streams, raw_cap, multi ? level : 0u, B, S)) return LFM_HIP_EINVAL;
+    count = B.nstreams;
     if ((size_t)count * B.cap >= (1ull << 32)) return LFM_HIP_EINVAL;
+    const bool parts = B.parts > 1;
 
     hipError_t e = hipSuccess;
     auto ok = [&]() { return (e = hipGetLastError()) == hipSuccess; };
@@ -3735,11 +4057,14 @@ extern "C" int lfm_hip_bzip2_blocks(const void* d_img, const uint32_t dims[5], c
     const bool from_img = ((uintptr_t)d_img & 15) == 0 && (bs[0] * bpp) % 16 == 0 && (dims[0] * bpp) % 16 == 0 &&
                           ((dims[0] % bs[0]) * bpp) % 16 == 0;
     mark(0);
-    if (from_img) {
-        hipLaunchKernelGGL(rle1_crc<true>, dim3(count), dim3(kRleThreads), 0, st, B);
+    if (!from_img) hipLaunchKernelGGL(gather_blocks, dim3(64, streams), dim3(256), 0, st, B);
+    if (!parts) {
+        if (from_img) hipLaunchKernelGGL((rle1_crc<true, false>), dim3(count), dim3(kRleThreads), 0, st, B);
+        else hipLaunchKernelGGL((rle1_crc<false, false>), dim3(count), dim3(kRleThreads), 0, st, B);
     } else {
-        hipLaunchKernelGGL(gather_blocks, dim3(64, count), dim3(256), 0, st, B);
-        hipLaunchKernelGGL(rle1_crc<false>, dim3(count), dim3(kRleThreads), 0, st, B);
+        if (from_img) hipLaunchKernelGGL((rle1_crc<true, true>), dim3(streams), dim3(kRleThreads), 0, st, B);
+        else hipLaunchKernelGGL((rle1_crc<false, true>), dim3(streams), dim3(kRleThreads), 0, st, B);
+        hipLaunchKernelGGL(place_parts, dim3(16, count), dim3(256), 0, st, B);
     }
     if (!ok()) return LFM_HIP_ERUNTIME;
     mark(1);
@@ -3810,9 +4135,19 @@ extern "C" int lfm_hip_bzip2_blocks(const void* d_img, const uint32_t dims[5], c
     hipLaunchKernelGGL(huff_final, dim3(count), dim3(64), 0, st, B);
     mark(4);
     const bool hook3 = t_hook && ev_tables && hipEventRecord(ev_tables, st) == hipSuccess;
-    hipLaunchKernelGGL(emit_stream, dim3(count), dim3(kEmitThreads), 0, st, B);
-    hipLaunchKernelGGL(scan_offsets, dim3(1), dim3(1024), 0, st, B.out_bytes, count, S.offs);
-    hipLaunchKernelGGL(compact_streams, dim3(count), dim3(256), 0, st, B, S.offs, (uint8_t*)d_payload);
+    Batch J = B;  // what compaction reads: the slots' streams, or the joined ones
+    if (!parts) {
+        hipLaunchKernelGGL(emit_stream<false>, dim3(count), dim3(kEmitThreads), 0, st, B);
+    } else {
+        hipLaunchKernelGGL(emit_stream<true>, dim3(count), dim3(kEmitThreads), 0, st, B);
+        hipLaunchKernelGGL(join_parts, dim3(streams), dim3(256), 0, st, B);
+        J.words = B.jwords;
+        J.out_cap = B.jcap;
+        J.out_bytes = B.sbytes;
+        J.flags = B.sflags;
+    }
+    hipLaunchKernelGGL(scan_offsets, dim3(1), dim3(1024), 0, st, J.out_bytes, streams, S.offs);
+    hipLaunchKernelGGL(compact_streams, dim3(streams), dim3(256), 0, st, J, S.offs, (uint8_t*)d_payload);
     mark(5);
     if (!ok()) return LFM_HIP_ERUNTIME;
     if (hook3 && hipEventSynchronize(ev_tables) == hipSuccess) t_hook(t_hook_ctx, 3);
@@ -3824,12 +4159,15 @@ extern "C" int lfm_hip_bzip2_blocks(const void* d_img, const uint32_t dims[5], c
                          "tied after the chunk sorts %u, runs left to the tie rounds %u\n", count, c[3], c[4],
                          bwt_stats.first_ties, bwt_stats.left_runs);
     }
-    std::vector<uint32_t> nbytes(count);
-    if (hipMemcpyAsync(nbytes.data(), B.out_bytes, count * 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
-        hipMemcpyAsync(h_flags, B.flags, count * 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
+    std::vector<uint32_t> nbytes(streams), np(streams, 1u);  // np: bzip2 blocks per stream
+    if (hipMemcpyAsync(nbytes.data(), J.out_bytes, streams * 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
+        hipMemcpyAsync(h_flags, J.flags, streams * 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
+        (parts && hipMemcpyAsync(np.data(), B.nparts, streams * 4, hipMemcpyDeviceToHost, st) != hipSuccess) ||
         hipStreamSynchronize(st) != hipSuccess)
         return LFM_HIP_ERUNTIME;
-    for (uint32_t i = 0; i < count; ++i) h_sizes[i] = nbytes[i];
+    for (uint32_t i = 0; i < streams; ++i) h_sizes[i] = nbytes[i];
+    t_last_blocks = 0;
+    for (uint32_t i = 0; i < streams; ++i) t_last_blocks += h_flags[i] ? 0u : np[i];
     if (timed) {
         SE.valid = true;
         for (int i = 0; i < 5; ++i)
@@ -3837,12 +4175,32 @@ extern "C" int lfm_hip_bzip2_blocks(const void* d_img, const uint32_t dims[5], c
     }
     return LFM_HIP_OK;
 }
+} // namespace
+
+extern "C" int lfm_hip_bzip2_blocks(const void* d_img, const uint32_t dims[5], const uint32_t bs[5], uint32_t bpp,
+                                    uint32_t first, uint32_t count, uint32_t level, void* d_ws, size_t ws_bytes,
+                                    void* d_payload, uint64_t* h_sizes, uint32_t* h_flags, void* stream)
+{
+    return bzip2_blocks(d_img, dims, bs, bpp, first, count, level, d_ws, ws_bytes, d_payload, h_sizes, h_flags, stream,
+                        false);
+}
+
+extern "C" int lfm_hip_bzip2_blocks_multi(const void* d_img, const uint32_t dims[5], const uint32_t bs[5],
+                                          uint32_t bpp, uint32_t first, uint32_t count, uint32_t level, void* d_ws,
+                                          size_t ws_bytes, void* d_payload, uint64_t* h_sizes, uint32_t* h_flags,
+                                          void* stream)
+{
+    return bzip2_blocks(d_img, dims, bs, bpp, first, count, level, d_ws, ws_bytes, d_payload, h_sizes, h_flags, stream,
+                        true);
+}
 
 extern "C" void lfm_hip_bzip2_set_stage_hook(void (*fn)(void*, int), void* ctx)
 {
     t_hook = fn;
     t_hook_ctx = ctx;
 }
+
+extern "C" uint64_t lfm_hip_bzip2_last_blocks(void) { return t_last_blocks; }
 
 extern "C" int lfm_hip_bzip2_last_stage_ms(float ms[5])
 {

@@ -268,6 +268,7 @@ int Encoder::wait(uint64_t ticket, const PinnedBuffer** out, lfm_encode_stats* s
         Inflight& f = fly_[p];
         if (f.ticket != ticket || ticket == 0) continue;
         if (f.th.joinable()) f.th.join();
+        last_counts = counts_[p];
         if (out) *out = &mem_ring[p];
         if (st) *st = f.st;
         return f.rc;
@@ -703,9 +704,21 @@ int Encoder::predictor_stage(const void* img, bool dev, klb_image_header& h, con
     return 0;
 }
 
+namespace {
+std::atomic<int>& multiblock_flag()
+{
+    static std::atomic<int> on{env_int("LFM_BZ2_MULTIBLOCK", 1) != 0 ? 1 : 0};
+    return on;
+}
+} // namespace
+
+int bzip2_multiblock() { return multiblock_flag().load(); }
+int set_bzip2_multiblock(int on) { return multiblock_flag().exchange(on ? 1 : 0); }
+
 // GPU bzip2 of every block (lfm_bzip2.hip), streams batched to bound the
-// workspace; streams the device hands back (RLE1 block reaching nblockMAX,
-// periodic blocks) are compressed by libbz2 here.  Same bytes either way.
+// workspace; streams the device hands back (periodic blocks; with
+// bzip2_multiblock() off also every stream libbzip2 cuts into several blocks)
+// are compressed by libbz2 here.  Same bytes either way.
 int Encoder::gpu_compress(const uint8_t* d_sym, klb_image_header& h, Sink& sink, lfm_encode_stats* st, int level,
                           int set, Inflight* fly)
 {
@@ -725,7 +738,15 @@ int Encoder::gpu_compress(const uint8_t* d_sym, klb_image_header& h, Sink& sink,
     // between the slots.
     static const long budget_mb = env_long("LFM_BZ2_GPU_BUDGET_MB", 0);  // (<= 0 means the default)
     static const size_t budget = (size_t)(budget_mb > 0 ? budget_mb : 48 * 1024) << 20;
-    const size_t per_stream = lfm_hip_bzip2_workspace_bytes(1, block_bytes) + out_cap;
+    // several bzip2 blocks per stream on the device: a stream takes one slot
+    // of the batch per block libbzip2 could cut (one for the default geometry:
+    // then both entry pairs are the same layout and launches)
+    const bool multi = bzip2_multiblock() != 0;
+    auto ws_bytes = [&](uint32_t n) {
+        return multi ? lfm_hip_bzip2_workspace_bytes_multi(n, block_bytes, (uint32_t)level)
+                     : lfm_hip_bzip2_workspace_bytes(n, block_bytes);
+    };
+    const size_t per_stream = ws_bytes(1) + out_cap;
     // one batch per slot (smaller batches, so the in-order writer's copies
     // overlap later batches' kernels, measured slower: the latency-bound
     // stages cost per batch)
@@ -733,10 +754,13 @@ int Encoder::gpu_compress(const uint8_t* d_sym, klb_image_header& h, Sink& sink,
     const uint64_t nway = slots;
     uint64_t batch = std::max<uint64_t>(1, std::min<uint64_t>((nblocks + nway - 1) / nway,
                                                                 budget / slots / per_stream));
-    batch = std::min<uint64_t>(batch, ((1ull << 32) - 1) / rle_cap);
+    // the slots' texts are indexed in 32 bits
+    batch = std::min<uint64_t>(batch, multi ? std::max<uint32_t>(1, lfm_hip_bzip2_max_count_multi(block_bytes, (uint32_t)level))
+                                            : ((1ull << 32) - 1) / rle_cap);
     const uint64_t nbatch = (nblocks + batch - 1) / batch;
     const int nslots = (int)std::min<uint64_t>(slots, nbatch);
-    const size_t ws = lfm_hip_bzip2_workspace_bytes((uint32_t)batch, block_bytes);
+    const size_t ws = ws_bytes((uint32_t)batch);
+    std::vector<uint64_t> gpu_blocks(nslots, 0);  // per slot, summed over its batches
     for (int k = 0; k < nslots; ++k) {
         BzSlot& sl = bz_[k];
         if (!sl.stream && hipStreamCreateWithFlags(&sl.stream, hipStreamNonBlocking) != hipSuccess) return 3;
@@ -827,8 +851,10 @@ int Encoder::gpu_compress(const uint8_t* d_sym, klb_image_header& h, Sink& sink,
                         }
                     },
                     &ro);
-            int ok = lfm_hip_bzip2_blocks(d_sym, dims, bs, (uint32_t)bpp, (uint32_t)b0, cnt, (uint32_t)level,
-                                          sl.d_ws.get(), ws, sl.d_out.get(), sizes[b].data(), flags[b].data(), sl.stream) == LFM_HIP_OK;
+            int ok = (multi ? lfm_hip_bzip2_blocks_multi : lfm_hip_bzip2_blocks)(
+                         d_sym, dims, bs, (uint32_t)bpp, (uint32_t)b0, cnt, (uint32_t)level, sl.d_ws.get(), ws,
+                         sl.d_out.get(), sizes[b].data(), flags[b].data(), sl.stream) == LFM_HIP_OK;
+            if (ok) gpu_blocks[k] += lfm_hip_bzip2_last_blocks();
             if (last) {
                 lfm_hip_bzip2_set_stage_hook(nullptr, nullptr);
                 if (!ro.done) fly->reach();
@@ -859,7 +885,7 @@ int Encoder::gpu_compress(const uint8_t* d_sym, klb_image_header& h, Sink& sink,
     std::vector<uint8_t> in(block_bytes), out((size_t)std::ceil((float)block_bytes * 2.0f + 50.0f));
     int rc = sink.begin(h);
     if (direct) sink.reserve_hint(h.getSizeInBytes() + nblocks * out_cap);
-    uint64_t offset = 0;
+    uint64_t offset = 0, host_streams = 0;
     for (uint64_t b = 0; b < nbatch && !rc; ++b) {
         {
             std::unique_lock<std::mutex> lk(mu);
@@ -904,6 +930,7 @@ int Encoder::gpu_compress(const uint8_t* d_sym, klb_image_header& h, Sink& sink,
                     h_all = (const uint8_t*)hs;
                 }
                 size_t n = 0;
+                ++host_streams;
                 gather_block(h_all, g, b0 + i, bpp, in.data(), &n);
                 uint32_t len = 0;
                 rc = compress_one(BZIP2, in.data(), (uint32_t)n, out.data(), (uint32_t)out.size(), &len, level);
@@ -929,6 +956,7 @@ int Encoder::gpu_compress(const uint8_t* d_sym, klb_image_header& h, Sink& sink,
     }
     cv.notify_all();
     for (auto& t : pool) t.join();
+    counts_[set] = StreamCounts{nblocks, host_streams, std::accumulate(gpu_blocks.begin(), gpu_blocks.end(), (uint64_t)0)};
     if (st) {
         for (double v : d2h) st->d2h_ms += v;
         for (int i = 0; i < 5; ++i)
@@ -994,7 +1022,9 @@ int Encoder::encode(const void* img, bool dev, klb_image_header& h, Sink& sink, 
                     const SlabSpec* slab)
 {
     join_inflight();  // a synchronous encode may use either buffer set
-    return encode_set(img, dev, h, sink, st, threads, slab, 0);
+    const int rc = encode_set(img, dev, h, sink, st, threads, slab, 0);
+    last_counts = counts_[0];
+    return rc;
 }
 
 int Encoder::encode_set(const void* img, bool dev, klb_image_header& h, Sink& sink, lfm_encode_stats* st,
@@ -1005,6 +1035,7 @@ int Encoder::encode_set(const void* img, bool dev, klb_image_header& h, Sink& si
     auto t0 = clk::now();
     if (st) std::memset(st, 0, sizeof(*st));
     const int level = slab_level(h, slab);
+    counts_[set] = StreamCounts{};
     if (int rc = normalize_header(h)) return rc;
     if (int rc = after_caller(dev)) return rc;
     const uint8_t* sym = nullptr;
@@ -1030,6 +1061,8 @@ int Encoder::encode_set(const void* img, bool dev, klb_image_header& h, Sink& si
         }
     } else {
         rc = compress_blocks(sym, h, sink, threads, level);
+        const uint64_t nb = BlockGrid(h).nblocks;
+        counts_[set] = StreamCounts{nb, nb, 0};
     }
     if (st) {
         st->compress_ms = ms_since(tc);

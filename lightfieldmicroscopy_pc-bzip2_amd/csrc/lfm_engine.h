@@ -136,6 +136,11 @@ struct SlabSpec {
 int normalize_header(klb_image_header& h);
 // bzip2 level of the reference's rule for the header's nominal block
 int bzip2_level(const klb_image_header& h);
+// GPU bzip2 of streams that libbzip2 cuts into several blocks (1, the default;
+// env LFM_BZ2_MULTIBLOCK) or their hand-back to the host library (0); the
+// setter returns the previous value
+int bzip2_multiblock();
+int set_bzip2_multiblock(int on);
 // multi-threaded memcpy (1 MiB pieces)
 void par_memcpy(void* dst, const void* src, size_t n, int threads);
 
@@ -167,6 +172,13 @@ public:
     // deferred copies
     int wait(uint64_t ticket, const PinnedBuffer** out, lfm_encode_stats* st);
     PinnedBuffer mem_ring[2];
+    // bzip2 streams of the last encode that encode() or wait() completed
+    // (lfm_encoder_stream_counts): all of them, those the host library
+    // compressed, and the bzip2 blocks the GPU produced
+    struct StreamCounts {
+        uint64_t streams = 0, host_streams = 0, bzip2_blocks = 0;
+    };
+    StreamCounts last_counts;
     // predictor selection on one host frame (uploaded to this encoder's device)
     int select_host_frame(const void* frame, int W, int H, int T, int family, int* chosen, float entropy[8]);
 
@@ -229,6 +241,7 @@ private:
     int after_caller(bool dev);
     void join_inflight();
     Inflight fly_[2];                         // by buffer set
+    StreamCounts counts_[2];                  // by buffer set: what its last encode compressed
     UploadPipe up_[2];                        // by buffer set
     hipStream_t up_stream_ = nullptr;         // host -> device chunk copies
     uint64_t next_ticket_ = 1;

@@ -40,13 +40,15 @@ EXPORTS = [
     "lfm_encoder_submit_select", "lfm_encoder_wait", "lfm_decode_memory_device", "lfm_decode_memory_roi_device",
     "lfm_set_decode_devices", "lfm_get_decode_devices", "lfm_default_decode_devices", "lfm_release_decoders",
     "lfm_decode_shard_plan", "lfm_decode_memory_multi", "lfm_decode_memory_multi_device",
+    "lfm_set_bzip2_multiblock", "lfm_get_bzip2_multiblock", "lfm_encoder_stream_counts",
     # lfm_hip.h
     "lfm_hip_predict", "lfm_hip_unpredict", "lfm_hip_unpredict_async", "lfm_hip_unpredict_check",
     "lfm_hip_unpredict_path",
     "lfm_hip_predict_candidates", "lfm_hip_entropy2d", "lfm_hip_select_workspace_bytes", "lfm_hip_select",
     "lfm_hip_synth", "lfm_hip_device_count", "lfm_hip_force_generic", "lfm_hip_bzip2_workspace_bytes", "lfm_hip_bzip2_out_cap",
     "lfm_hip_bzip2_blocks", "lfm_hip_bzip2_last_stage_ms", "lfm_hip_bunzip2_workspace_bytes", "lfm_hip_bunzip2_blocks", "lfm_hip_scatter_blocks",
-    "lfm_hip_crop_region",
+    "lfm_hip_crop_region", "lfm_hip_bzip2_workspace_bytes_multi", "lfm_hip_bzip2_max_count_multi",
+    "lfm_hip_bzip2_blocks_multi", "lfm_hip_bzip2_last_blocks",
 ]
 
 
@@ -177,6 +179,16 @@ def lib():
     L.lfm_hip_bzip2_blocks.argtypes = [vp, u32p, u32p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
                                        ctypes.c_uint32, vp, ctypes.c_size_t, vp,
                                        ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint32), vp]
+    L.lfm_hip_bzip2_workspace_bytes_multi.argtypes = [ctypes.c_uint32] * 3
+    L.lfm_hip_bzip2_workspace_bytes_multi.restype = ctypes.c_size_t
+    L.lfm_hip_bzip2_max_count_multi.argtypes = [ctypes.c_uint32] * 2
+    L.lfm_hip_bzip2_max_count_multi.restype = ctypes.c_uint32
+    L.lfm_hip_bzip2_blocks_multi.argtypes = L.lfm_hip_bzip2_blocks.argtypes
+    L.lfm_hip_bzip2_last_blocks.argtypes = []
+    L.lfm_hip_bzip2_last_blocks.restype = ctypes.c_uint64
+    L.lfm_set_bzip2_multiblock.argtypes = [ctypes.c_int]
+    L.lfm_get_bzip2_multiblock.argtypes = []
+    L.lfm_encoder_stream_counts.argtypes = [vp] + [ctypes.POINTER(ctypes.c_uint64)] * 3
     L.lfm_hip_bunzip2_workspace_bytes.argtypes = [ctypes.c_uint32, ctypes.c_uint32]
     L.lfm_hip_bunzip2_workspace_bytes.restype = ctypes.c_size_t
     L.lfm_hip_bunzip2_blocks.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64), ctypes.c_uint32, vp, ctypes.c_uint32,
@@ -373,6 +385,15 @@ class Encoder:
         if self._h:
             lib().lfm_encoder_destroy(self._h)
             self._h = None
+
+    def stream_counts(self):
+        """How the bzip2 streams of the last encode()/encode_slab()/wait() on
+        this encoder were compressed: {"streams", "host_streams" (by the host
+        library), "bzip2_blocks" (bzip2 blocks the GPU produced)}.  All 0 after
+        encode_multi(), which encodes on other encoders."""
+        v = [ctypes.c_uint64() for _ in range(3)]
+        _check(lib().lfm_encoder_stream_counts(self._h, *[ctypes.byref(x) for x in v]), "lfm_encoder_stream_counts")
+        return {"streams": v[0].value, "host_streams": v[1].value, "bzip2_blocks": v[2].value}
 
     def __del__(self):
         try:
@@ -895,24 +916,40 @@ def entropy_device(d_cand, npix=None, stream=None):
     return e.value
 
 
-def bzip2_device(d_img, dims, block, bpp, level=None, first=0, count=None, stream=None):
+def set_bzip2_multiblock(on):
+    """GPU bzip2 of streams of several bzip2 blocks on (default) or off (such
+    streams go to the host library); returns the previous setting."""
+    return bool(lib().lfm_set_bzip2_multiblock(1 if on else 0))
+
+
+def get_bzip2_multiblock():
+    return bool(lib().lfm_get_bzip2_multiblock())
+
+
+def bzip2_device(d_img, dims, block, bpp, level=None, first=0, count=None, stream=None, multi=False):
     """GPU bzip2 of the x-fastest block grid of a device image (torch tensor
     holding dims[4]*...*dims[0]*bpp bytes).  Returns ([bytes or None per
-    stream], flags): None where the stream was handed to the host library."""
+    stream], flags): None where the stream was handed to the host library.
+    multi=True: lfm_hip_bzip2_blocks_multi, which also compresses the streams
+    libbzip2 cuts into several bzip2 blocks."""
     nb = [-(-d // b) for d, b in zip(dims, block)]
     total = int(np.prod(nb))
     count = total - first if count is None else count
     block_bytes = int(np.prod(block)) * bpp
     level = min(9, -(-block_bytes // 100000)) if level is None else level
-    ws_bytes = lib().lfm_hip_bzip2_workspace_bytes(count, block_bytes)
+    if multi:
+        ws_bytes = lib().lfm_hip_bzip2_workspace_bytes_multi(count, block_bytes, level)
+    else:
+        ws_bytes = lib().lfm_hip_bzip2_workspace_bytes(count, block_bytes)
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=d_img.device)
     out_cap = lib().lfm_hip_bzip2_out_cap(block_bytes)
     pay = torch.empty(count * out_cap, dtype=torch.uint8, device=d_img.device)
     sizes = (ctypes.c_uint64 * count)()
     flags = (ctypes.c_uint32 * count)()
-    _check(lib().lfm_hip_bzip2_blocks(d_img.data_ptr(), _u32(dims), _u32(block), bpp, first, count, level,
-                                      ws.data_ptr(), ws_bytes, pay.data_ptr(), sizes, flags, _stream(stream)),
-           "lfm_hip_bzip2_blocks")
+    fn = lib().lfm_hip_bzip2_blocks_multi if multi else lib().lfm_hip_bzip2_blocks
+    _check(fn(d_img.data_ptr(), _u32(dims), _u32(block), bpp, first, count, level,
+              ws.data_ptr(), ws_bytes, pay.data_ptr(), sizes, flags, _stream(stream)),
+           "lfm_hip_bzip2_blocks_multi" if multi else "lfm_hip_bzip2_blocks")
     host = pay[:int(sum(sizes))].cpu().numpy().tobytes()
     out, o = [], 0
     for i in range(count):
