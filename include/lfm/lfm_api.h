@@ -178,6 +178,18 @@ LFM_API int lfm_encoder_encode_multi(lfm_encoder* enc, const void* img, const ui
  * returns the previous value; it applies to encodes started after it. */
 LFM_API int lfm_set_bzip2_multiblock(int on);
 LFM_API int lfm_get_bzip2_multiblock(void);
+/* The reader's side of the same.  1 (the default; env
+ * LFM_BUNZIP2_MULTIBLOCK=0 starts with 0): streams of several bzip2 blocks are
+ * decoded on the GPU like single-block ones, in every reader that decodes on
+ * the GPU (whole images and regions, host and device destinations, one device
+ * or several); only streams with a periodic block (and malformed ones) still
+ * go to the host library.  0: every such stream is decoded by the host
+ * library, one after the other, as before this switch existed.  The pixels
+ * are the same either way; lfm_decode_stats.host_blocks tells the two apart.
+ * The setter returns the previous value; it applies to decodes started after
+ * it. */
+LFM_API int lfm_set_bunzip2_multiblock(int on);
+LFM_API int lfm_get_bunzip2_multiblock(void);
 /* How the bzip2 streams (one per 5-D block) of the last encode were compressed
  * that lfm_encoder_encode, lfm_encoder_encode_slab or lfm_encoder_wait
  * completed on this encoder: all streams, those the host library compressed,

@@ -156,6 +156,33 @@ int lfm_hip_bunzip2_blocks(const void* d_payload, const uint64_t* h_offs, uint32
 int lfm_hip_bunzip2_issue(const void* d_payload, const uint64_t* h_offs, uint32_t count, void* d_out,
                           uint32_t out_stride, void* d_ws, size_t ws_bytes, uint32_t* h_lens, uint32_t* h_flags,
                           void* stream);
+/* The same pair for streams of several bzip2 blocks (what libbzip2 and
+ * lfm_hip_bzip2_blocks_multi write for a block above ~900 kB, or a smaller one
+ * that grows under RLE1).  `level` (1..9) is the batch's bzip2 level: a stream
+ * takes lfm_hip_bunzip2_max_parts(out_stride, level) slots of the workspace
+ * (the encoder's bound: the worst-case RLE1 length, 5/4 of out_stride, over
+ * nblockMAX(level)), each sized for one bzip2 block of that level.  One wave
+ * still reads a stream's blocks one after the other (a block's start is known
+ * once the block before it is decoded); the inverse BWT and the RLE1 decode
+ * run per block, each block's bytes landing behind those of the blocks before
+ * it, each checked against its own CRC and the stream's combined CRC against
+ * their fold.  h_lens[i] is the stream's decoded length and h_flags[i] as
+ * above: 1 for a stream with more blocks than slots, a block above the
+ * level's size, a periodic block, a damaged magic or combined CRC or more
+ * than out_stride decoded bytes (nothing of a part that does not fit is
+ * written); 2 when a block's bytes do not match its CRC.  Where max_parts is 1
+ * (the default 96x96x8 uint16 block at its level 2) the size, the layout and
+ * the launches are those of the single-block pair.  The workspace is
+ * lfm_hip_bunzip2_workspace_bytes_multi(count, out_stride, level); a level
+ * outside 1..9 gives 0 there, 0 parts and LFM_HIP_EINVAL here. */
+uint32_t lfm_hip_bunzip2_max_parts(uint32_t out_stride, uint32_t level);
+size_t lfm_hip_bunzip2_workspace_bytes_multi(uint32_t count, uint32_t out_stride, uint32_t level);
+int lfm_hip_bunzip2_blocks_multi(const void* d_payload, const uint64_t* h_offs, uint32_t count, void* d_out,
+                                 uint32_t out_stride, uint32_t level, void* d_ws, size_t ws_bytes, uint32_t* h_lens,
+                                 uint32_t* h_flags, void* stream);
+int lfm_hip_bunzip2_issue_multi(const void* d_payload, const uint64_t* h_offs, uint32_t count, void* d_out,
+                                uint32_t out_stride, uint32_t level, void* d_ws, size_t ws_bytes, uint32_t* h_lens,
+                                uint32_t* h_flags, void* stream);
 
 /* Decoded blocks first .. first + count - 1 (block i at d_blocks + (i -
  * first) * stride, x fastest) back into the device image (the inverse of the

@@ -187,6 +187,8 @@ extern "C" int lfm_encoder_encode_multi(lfm_encoder* e, const void* img, const u
 
 extern "C" int lfm_set_bzip2_multiblock(int on) { return lfm::set_bzip2_multiblock(on); }
 extern "C" int lfm_get_bzip2_multiblock(void) { return lfm::bzip2_multiblock(); }
+extern "C" int lfm_set_bunzip2_multiblock(int on) { return lfm::set_bunzip2_multiblock(on); }
+extern "C" int lfm_get_bunzip2_multiblock(void) { return lfm::bunzip2_multiblock(); }
 
 extern "C" int lfm_encoder_stream_counts(lfm_encoder* e, uint64_t* streams, uint64_t* host_streams,
                                          uint64_t* bzip2_blocks)

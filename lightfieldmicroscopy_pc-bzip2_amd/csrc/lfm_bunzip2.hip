@@ -28,6 +28,20 @@
 //               resolved by running every start state), CRC-32 of the block in
 //               64 segments combined by polynomial shifts, checked against the
 //               header.
+//
+// A stream of several bzip2 blocks (what libbzip2 writes for a block above
+// ~900 kB, or a smaller one whose data grows under RLE1) decodes through the
+// _multi entries: as in the encoder (lfm_bzip2.hip) a stream owns `parts`
+// consecutive slots of the workspace, one per bzip2 block ("part"), each with
+// its own ll / tt / marker / kept-byte regions and its own n, origPtr, CRC and
+// flag.  bzd_huff<.., MULTI> still runs one wave per stream and walks the
+// stream's blocks one after the other with one bit reader (a block's start is
+// known only once the block before it is decoded), filling slot after slot;
+// bzd_tt, bzd_walk and bzd_rle1 then run per slot exactly as they run per
+// stream, bzd_rle1 placing part p behind the decoded bytes of the parts before
+// it, and bzd_status folds the slots' lengths and flags into the per-stream
+// results.  With parts == 1 the _multi entries are the single-block ones: the
+// same layout and the same kernels.
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <cstdint>
@@ -35,6 +49,7 @@
 #include <cstring>
 #include <vector>
 #include "lfm_hip.h"
+#include "lfm_bz_caps.h"  // max_parts
 
 #ifndef LFM_BZD_PROBE
 #define LFM_BZD_PROBE 0  // timing probes of bzd_huff (scripts only; 0 in the library)
@@ -79,6 +94,12 @@ struct Dec {
     uint32_t* flags;
     uint32_t* out_len;
     uint32_t sel_cap;         // selectors that fit the decoder's LDS
+    // several bzip2 blocks per stream (the MULTI kernels): stream s owns slots
+    // s * parts .. s * parts + parts - 1, and every per-stream region and word
+    // above is per slot
+    uint32_t parts;
+    uint32_t* s_len;          // per stream: decoded bytes
+    uint32_t* s_flag;         // per stream: 0, kHost or kCrcFail
 };
 
 // MSB-first bit reader over the payload: a 64-bit window of two big-endian
@@ -150,6 +171,13 @@ struct BitReader {
 //    and the decode is bound by that code: ~16 waves per CU share one scalar
 //    unit (PMC: 43 SALU + 20 VALU + 11 branch instructions per symbol before).
 // Output: the BWT last column ll[], n, origPtr, the block CRC.
+// MULTI: the same wave goes on into the stream's next bzip2 block where the
+// single-block form demands the end of the stream: the bit reader carries on,
+// everything else a block sets up (mapping table, selectors, tables, the
+// move-to-front list, nblock, the open run) starts afresh, and the output
+// moves to the stream's next slot.  The symbol loop is the same code: what
+// the blocks share (the part index, the folded CRC) is wave-uniform and lives
+// in scalar registers, and the LDS is the single-block form's.
 struct WaveBits {
     const uint32_t* w;   // the stream's first (aligned) payload word
     uint32_t nw;         // words that start inside the stream (later ones read as 0)
@@ -294,7 +322,7 @@ __device__ __forceinline__ uint32_t wave_sum_incl(uint32_t x)
     return x;
 }
 
-template <int LB, bool VB>
+template <int LB, bool VB, bool MULTI>
 __global__ __launch_bounds__(64) void bzd_huff(Dec D)
 {
     __shared__ uint16_t lut[kMaxGroups << LB];
@@ -313,19 +341,27 @@ __global__ __launch_bounds__(64) void bzd_huff(Dec D)
     WaveBits br;
     const uint64_t b0 = D.offs[s], b1 = D.offs[s + 1];
     br.init(D.payload, b0, b1);
-    uint8_t* ll = D.ll + (size_t)s * D.cap;
+    const uint32_t slot0 = MULTI ? s * D.parts : s;  // the stream's first slot
+    uint8_t* ll = D.ll + (size_t)slot0 * D.cap;
     uint32_t nblock = 0, origPtr = 0, bcrc = 0;
     uint32_t s2u = 0;  // seqToUnseq, entries 4 * lane .. 4 * lane + 3
+    uint32_t p = 0, comb = 0;  // MULTI: the block's index in the stream, the CRCs of the blocks before it folded
     // LDS reads of wave-uniform values go through readfirstlane so that the
     // decode's control flow stays scalar
     auto U = [](uint32_t x) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)x); };
-    do {
-        if (b1 - b0 < 14) { flag = kHost; break; }
-        if (br.get(24) != 0x425A68u) { flag = kHost; break; }  // "BZh"
-        const uint32_t lv = br.get(8);
-        if (lv < '1' || lv > '9') { flag = kHost; break; }
-        const uint32_t m1 = br.get(24), m2 = br.get(24);
-        if (m1 != 0x314159u || m2 != 0x265359u) { flag = kHost; break; }  // no block (empty) or damaged
+    // one turn per bzip2 block (one turn without MULTI); a break ends the
+    // stream, decoded or flagged
+    for (;;) {
+        if (p == 0) {
+            if (b1 - b0 < 14) { flag = kHost; break; }
+            if (br.get(24) != 0x425A68u) { flag = kHost; break; }  // "BZh"
+            const uint32_t lv = br.get(8);
+            if (lv < '1' || lv > '9') { flag = kHost; break; }
+            const uint32_t m1 = br.get(24), m2 = br.get(24);
+            if (m1 != 0x314159u || m2 != 0x265359u) { flag = kHost; break; }  // no block (empty) or damaged
+        }
+        nblock = 0;
+        s2u = 0;
         bcrc = br.get(32);
         if (br.get(1)) { flag = kHost; break; }  // randomised block (bzip2 0.9.0 style)
         origPtr = br.get(24);
@@ -608,20 +644,49 @@ __global__ __launch_bounds__(64) void bzd_huff(Dec D)
         if (flag) break;
         if constexpr (VB) lb.to(br);
         if (origPtr >= nblock || nblock == 0) { flag = kHost; break; }
-        // end of stream: exactly one block
         const uint32_t e1 = br.get(24), e2 = br.get(24);
+        if constexpr (MULTI) {
+            // the block is whole: its slot's words, then the next block if its
+            // magic follows and the stream has a slot left for it
+            comb = ((comb << 1) | (comb >> 31)) ^ bcrc;
+            if (lane == 0) {
+                D.n[slot0 + p] = nblock;
+                D.orig[slot0 + p] = origPtr;
+                D.crc[slot0 + p] = bcrc;
+            }
+            if (e1 == 0x314159u && e2 == 0x265359u) {
+                if (br.over() || p + 1 == D.parts) { flag = kHost; break; }
+                ++p;
+                ll += D.cap;
+                continue;
+            }
+        }
+        // end of stream (without MULTI: after exactly one block)
         if (e1 != 0x177245u || e2 != 0x385090u) { flag = kHost; break; }
         const uint32_t ccrc = br.get(32);
-        if (ccrc != bcrc) { flag = kHost; break; }  // one block: combined CRC = rotl(0, 1) ^ blockCRC
-    } while (false);
+        // (one block: combined CRC = rotl(0, 1) ^ blockCRC)
+        if (ccrc != (MULTI ? comb : bcrc) || (MULTI && br.over())) flag = kHost;
+        break;
+    }
 #if LFM_BZD_PROBE
     if (flag) flag = kCrcFail;  // (never the host library: the probes' streams are not decoded)
 #endif
     if (lane == 0) {
-        D.flags[s] = flag;
-        D.n[s] = flag ? 0u : nblock;
-        D.orig[s] = origPtr;
-        D.crc[s] = bcrc;
+        if constexpr (MULTI) {
+            // every slot of the stream carries the stream's flag; the slots
+            // past the last block (all of them when flagged) are unused: n = 0
+            // (the same lane wrote the used slots' n above, so these stores
+            // come after those)
+            for (uint32_t q = 0; q < D.parts; ++q) {
+                D.flags[slot0 + q] = flag;
+                if (flag || q > p) D.n[slot0 + q] = 0u;
+            }
+        } else {
+            D.flags[s] = flag;
+            D.n[s] = flag ? 0u : nblock;
+            D.orig[s] = origPtr;
+            D.crc[s] = bcrc;
+        }
     }
 }
 
@@ -633,7 +698,9 @@ constexpr int kTtThreads = 256;
 // loads of a tile, each used right away, made all three passes wait one
 // memory latency per 256 positions (ll and tt live in 256-aligned stream
 // regions of cap bytes / words, so whole 16-byte chunks up to n stay inside)
-template <int NT>
+// MULTI (here and in bzd_walk): the grid runs over slots, s is a slot; a slot
+// past its stream's last block has n == 0 and is skipped like a flagged one
+template <int NT, bool MULTI>
 __global__ __launch_bounds__(NT) void bzd_tt(Dec D)
 {
     constexpr uint32_t kBlk = 16u * NT;  // ll bytes per staged block (16 tiles)
@@ -644,6 +711,7 @@ __global__ __launch_bounds__(NT) void bzd_tt(Dec D)
     const uint32_t s = blockIdx.x, t = threadIdx.x, lane = t & 63, wave = t >> 6;
     if (D.flags[s]) return;
     const uint32_t n = D.n[s];
+    if (MULTI && n == 0) return;
     const uint8_t* ll = D.ll + (size_t)s * D.cap;
     uint32_t* tt = D.tt + (size_t)s * D.cap;
     const uint32_t nch = (n + 15u) / 16u;  // 16-byte chunks of ll
@@ -767,7 +835,7 @@ __device__ __forceinline__ uint32_t marker_id(uint32_t j, uint32_t v0, uint32_t 
 // LDSM: the marker tables (successor, length, output offset, restart node)
 // live in LDS, so the one-lane chaining of the segments reads LDS instead of
 // making ~1 150 dependent global round trips per stream
-template <int NT, bool LDSM>
+template <int NT, bool LDSM, bool MULTI>
 __global__ __launch_bounds__(NT) void bzd_walk(Dec D)
 {
     extern __shared__ uint32_t wsm[];  // LDSM: 4 x mcap words
@@ -775,6 +843,7 @@ __global__ __launch_bounds__(NT) void bzd_walk(Dec D)
     const uint32_t s = blockIdx.x, t = threadIdx.x;
     if (D.flags[s]) return;
     const uint32_t n = D.n[s];
+    if (MULTI && n == 0) return;
     const uint32_t* tt = D.tt + (size_t)s * D.cap;
     uint8_t* rle = D.rle + (size_t)s * D.cap;
     uint32_t* mnext = LDSM ? wsm : D.mnext + (size_t)s * D.mcap;
@@ -941,25 +1010,32 @@ __device__ __forceinline__ uint32_t chunk_byte(const uint4& q, int j)  // j comp
     return (w >> (8 * (j & 3))) & 0xFFu;
 }
 
-__global__ __launch_bounds__(64) void bzd_rle1(Dec D)
+//
+// MULTI: one wave per slot (s is a slot).  Every bzip2 block is RLE1-decoded
+// on its own (libbzip2 resets the run state per block), so part p of a stream
+// differs only in where its bytes go: behind the decoded bytes of parts 0 ..
+// p - 1.  The wave gets those lengths by running steps A and B over the
+// earlier parts' texts first (p more text reads; the stream's first part,
+// which is the longest chain of work, has none), then its own.
+struct RleLds {
+    uint32_t smap[64], scnt[5][64], sst[64], soff[64];
+    uint32_t total;
+};
+
+// Steps A and B over the text of slot q: this lane's segment [a, b) and the
+// text byte before it, the lanes' start states and output offsets (L.sst,
+// L.soff); returns the decoded length.
+__device__ __forceinline__ uint32_t rle1_scan(const Dec& D, uint32_t q, uint32_t lane, RleLds& L, uint32_t& a,
+                                              uint32_t& b, uint32_t& before)
 {
-    __shared__ uint32_t T1[256];
-    __shared__ uint32_t smap[64], scnt[5][64], sst[64], soff[64];
-    __shared__ uint32_t s_total;
-    const uint32_t lane = threadIdx.x, s = blockIdx.x;
-    for (uint32_t i = lane; i < 256; i += 64) T1[i] = c_dcrc[i];
-    if (D.flags[s]) {
-        if (lane == 0) D.out_len[s] = 0;
-        return;
-    }
-    const uint32_t n = D.n[s];
-    const uint8_t* rle = D.rle + (size_t)s * D.cap;
-    uint8_t* out = D.out + (size_t)s * D.out_stride;
-    const uint32_t cap = D.out_stride;
+    uint32_t(&smap)[64] = L.smap, (&scnt)[5][64] = L.scnt, (&sst)[64] = L.sst, (&soff)[64] = L.soff;
+    const uint32_t n = D.n[q];
+    const uint8_t* rle = D.rle + (size_t)q * D.cap;
     const TextChunks tx{rle, D.cap};
     const uint32_t seg = ((n + 63) / 64 + kRleSeg - 1) / kRleSeg * kRleSeg;
-    const uint32_t a = min(n, lane * seg), b = min(n, a + seg);
-    const uint32_t before = a ? (uint32_t)rle[a - 1] : 256u;  // the text byte before the segment
+    a = min(n, lane * seg);
+    b = min(n, a + seg);
+    before = a ? (uint32_t)rle[a - 1] : 256u;  // the text byte before the segment
     // A: all five start states until their paths meet, then one path
     {
         uint32_t st[5] = {0, 1, 2, 3, 4}, cnt[5] = {0, 0, 0, 0, 0};
@@ -1014,17 +1090,49 @@ __global__ __launch_bounds__(64) void bzd_rle1(Dec D)
             off += scnt[stt][l];
             stt = (smap[l] >> (3 * stt)) & 7u;
         }
-        s_total = off;
+        L.total = off;
     }
     __syncthreads();
-    const uint32_t tot = s_total;
-    if (tot > cap) {
+    return L.total;
+}
+
+template <bool MULTI>
+__global__ __launch_bounds__(64) void bzd_rle1(Dec D)
+{
+    __shared__ uint32_t T1[256];
+    __shared__ RleLds L;
+    const uint32_t lane = threadIdx.x, s = blockIdx.x;
+    for (uint32_t i = lane; i < 256; i += 64) T1[i] = c_dcrc[i];
+    if (D.flags[s] || (MULTI && D.n[s] == 0)) {
+        if (lane == 0) D.out_len[s] = 0;
+        return;
+    }
+    const uint32_t strm = MULTI ? s / D.parts : s;
+    uint32_t a, b, before;
+    // MULTI: the decoded bytes of the stream's earlier parts (a sum that
+    // passes out_stride is the overflow below whatever comes after)
+    uint64_t base = 0;
+    if constexpr (MULTI)
+        for (uint32_t q = strm * D.parts; q < s; ++q) {
+            base += rle1_scan(D, q, lane, L, a, b, before);
+            __syncthreads();  // L is read before the next scan rewrites it
+        }
+    const uint32_t tot = rle1_scan(D, s, lane, L, a, b, before);
+    const uint32_t(&sst)[64] = L.sst, (&soff)[64] = L.soff;
+    const TextChunks tx{D.rle + (size_t)s * D.cap, D.cap};
+    if (base + tot > D.out_stride) {  // the stream does not fit its output: nothing of this part is written
         if (lane == 0) {
             D.out_len[s] = tot;
             D.flags[s] = kHost;
         }
         return;
     }
+    // MULTI: out is any byte of the stream's region.  The store scheme below
+    // never relied on its alignment (ab), and a whole 16-byte piece lies
+    // strictly inside one lane's own output range [o, oend), which lies
+    // inside this part's [base, base + tot): two parts never share a vector
+    // store, and the bytes at a part's ends go one by one.
+    uint8_t* out = D.out + (size_t)strm * D.out_stride + base;
     // C: decode the segment from its start state.  Whole aligned 16-byte
     // pieces of the lane's output leave as one store each (byte stores made
     // every store instruction touch 64 scattered lines); the partial pieces at
@@ -1106,6 +1214,24 @@ __global__ __launch_bounds__(64) void bzd_rle1(Dec D)
     }
 }
 
+// The slots' lengths and flags folded into the stream's (one thread per
+// stream): the decoded bytes of its parts, and kHost from any slot before
+// kCrcFail from any slot (a stream the host decodes again is not a read error
+// yet).  Unused slots carry length 0 and their stream's flag.
+__global__ __launch_bounds__(256) void bzd_status(Dec D)
+{
+    const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= D.count) return;
+    uint32_t len = 0, flag = 0;
+    for (uint32_t q = s * D.parts; q < (s + 1) * D.parts; ++q) {
+        const uint32_t f = D.flags[q];
+        flag = (f == kHost || flag == kHost) ? kHost : (f ? f : flag);
+        len += D.out_len[q];
+    }
+    D.s_len[s] = len;
+    D.s_flag[s] = flag;
+}
+
 } // namespace bzd
 } // namespace lfm
 
@@ -1115,33 +1241,84 @@ namespace {
 
 size_t al(size_t v) { return (v + 255) / 256 * 256; }
 
-uint32_t dec_cap(uint32_t out_stride)
-{
-    // a .lfm block of B bytes is compressed at level min(9, ceil(B / 1e5))
-    // (klb_imageIO.cpp:108): its RLE1 block is at most 100000 * level bytes
-    const uint32_t level = std::min<uint32_t>(9, std::max<uint32_t>(1, (out_stride + 99999) / 100000));
-    return (uint32_t)al(100000u * level + 64);
-}
+// a .lfm block of B bytes is compressed at level min(9, ceil(B / 1e5))
+// (klb_imageIO.cpp:108)
+uint32_t level_of(uint32_t out_stride) { return std::min<uint32_t>(9, std::max<uint32_t>(1, (out_stride + 99999) / 100000)); }
+
+// the RLE1 block of one bzip2 block of `level` is at most 100000 * level bytes
+// (nblockMAX + 5 = 100000 * level - 14 at the most)
+uint32_t dec_cap(uint32_t level) { return (uint32_t)al(100000u * level + 64); }
 
 uint32_t mark_cap(uint32_t cap) { return (cap + kMark - 1) / kMark + 2; }
+
+// The workspace, described once: every buffer in order, 256-byte aligned.
+// With base == nullptr this only sums (the workspace_bytes entries); with the
+// workspace base it also points D into it.  A stream owns `parts` slots, each
+// sized for one bzip2 block of `level`; the per-stream results follow the
+// slots' words when there is more than one slot per stream (with one, a slot's
+// words are the stream's, and the layout is the one
+// lfm_hip_bunzip2_workspace_bytes has always described).
+size_t layout(uint8_t* base, uint32_t count, uint32_t level, uint32_t parts, Dec& D)
+{
+    const size_t slots = (size_t)count * parts;
+    D.count = count;
+    D.parts = parts;
+    D.cap = dec_cap(level);
+    D.mcap = mark_cap(D.cap);
+    size_t used = 0;
+    auto take = [&](size_t bytes) {
+        uint8_t* r = base ? base + used : nullptr;
+        used += al(bytes);
+        return r;
+    };
+    D.offs = (const uint64_t*)take(((size_t)count + 1) * 8);
+    D.ll = take(slots * D.cap);  // ll, then the RLE1 text (ll is dead once tt holds its bytes)
+    D.tt = (uint32_t*)take(slots * D.cap * 4);
+    D.rle = D.ll;  // bzd_walk writes the text over ll (bzd_tt copied ll into tt)
+    D.mnext = (uint32_t*)take(slots * D.mcap * 4);
+    D.mlen = (uint32_t*)take(slots * D.mcap * 4);
+    D.mstart = (uint32_t*)take(slots * D.mcap * 4);
+    D.mres = (uint32_t*)take(slots * D.mcap * 4);
+    D.wkeep = take(slots * D.mcap * kWalkKeep);  // walkers' kept bytes
+    uint32_t** small[] = {&D.n, &D.orig, &D.crc, &D.flags, &D.out_len};
+    for (uint32_t** q : small) *q = (uint32_t*)take(slots * 4 + 64);
+    (void)take(slots * 4 + 64);
+    D.s_len = D.out_len;
+    D.s_flag = D.flags;
+    if (parts > 1) {
+        D.s_len = (uint32_t*)take((size_t)count * 4 + 64);
+        D.s_flag = (uint32_t*)take((size_t)count * 4 + 64);
+    }
+    return used;
+}
 
 uint32_t host_dcrc[256];
 uint32_t host_xpow[24];
 bool dcrc_ready = false;
 
+// level 0: the single-block entries (one slot per stream, the level from
+// out_stride); 1..9: the _multi entries
+int issue(const void* d_payload, const uint64_t* h_offs, uint32_t count, void* d_out, uint32_t out_stride,
+          uint32_t level, void* d_ws, size_t ws_bytes, uint32_t* h_lens, uint32_t* h_flags, hipStream_t st);
+
 } // namespace
 
 extern "C" size_t lfm_hip_bunzip2_workspace_bytes(uint32_t count, uint32_t out_stride)
 {
-    const size_t cap = dec_cap(out_stride), mc = mark_cap((uint32_t)cap);
-    size_t b = 0;
-    b += al(((size_t)count + 1) * 8);
-    b += al((size_t)count * cap);          // ll, then the RLE1 text (ll is dead once tt holds its bytes)
-    b += al((size_t)count * cap * 4);      // tt
-    b += 4 * al((size_t)count * mc * 4);
-    b += al((size_t)count * mc * kWalkKeep);  // walkers' kept bytes
-    b += 6 * al((size_t)count * 4 + 64);
-    return b;
+    Dec D{};
+    return layout(nullptr, count, level_of(out_stride), 1, D);
+}
+
+extern "C" uint32_t lfm_hip_bunzip2_max_parts(uint32_t out_stride, uint32_t level)
+{
+    return level < 1 || level > 9 ? 0u : lfm::bz::max_parts(out_stride, level);
+}
+
+extern "C" size_t lfm_hip_bunzip2_workspace_bytes_multi(uint32_t count, uint32_t out_stride, uint32_t level)
+{
+    if (level < 1 || level > 9) return 0;
+    Dec D{};
+    return layout(nullptr, count, level, lfm::bz::max_parts(out_stride, level), D);
 }
 
 // Decode streams [0, count) of the device payload (byte ranges h_offs[i] ..
@@ -1164,9 +1341,60 @@ extern "C" int lfm_hip_bunzip2_issue(const void* d_payload, const uint64_t* h_of
                                      uint32_t out_stride, void* d_ws, size_t ws_bytes, uint32_t* h_lens,
                                      uint32_t* h_flags, void* stream_)
 {
-    hipStream_t st = (hipStream_t)stream_;
+    return issue(d_payload, h_offs, count, d_out, out_stride, 0, d_ws, ws_bytes, h_lens, h_flags, (hipStream_t)stream_);
+}
+
+// The two entries for streams of several bzip2 blocks (`level`: the batch's
+// bzip2 level, 1..9; a stream may hold up to lfm_hip_bunzip2_max_parts blocks,
+// each of at most that level's size)
+extern "C" int lfm_hip_bunzip2_blocks_multi(const void* d_payload, const uint64_t* h_offs, uint32_t count, void* d_out,
+                                            uint32_t out_stride, uint32_t level, void* d_ws, size_t ws_bytes,
+                                            uint32_t* h_lens, uint32_t* h_flags, void* stream_)
+{
+    const int rc = lfm_hip_bunzip2_issue_multi(d_payload, h_offs, count, d_out, out_stride, level, d_ws, ws_bytes,
+                                               h_lens, h_flags, stream_);
+    if (rc != LFM_HIP_OK) return rc;
+    return hipStreamSynchronize((hipStream_t)stream_) == hipSuccess ? LFM_HIP_OK : LFM_HIP_ERUNTIME;
+}
+
+extern "C" int lfm_hip_bunzip2_issue_multi(const void* d_payload, const uint64_t* h_offs, uint32_t count, void* d_out,
+                                           uint32_t out_stride, uint32_t level, void* d_ws, size_t ws_bytes,
+                                           uint32_t* h_lens, uint32_t* h_flags, void* stream_)
+{
+    if (level < 1 || level > 9) return LFM_HIP_EINVAL;
+    return issue(d_payload, h_offs, count, d_out, out_stride, level, d_ws, ws_bytes, h_lens, h_flags,
+                 (hipStream_t)stream_);
+}
+
+namespace {
+
+template <bool MULTI>
+void launch(const Dec& D, uint32_t slots, hipStream_t st)
+{
+    const size_t sel_lds = ((D.sel_cap + 7) / 8 * 4 + 15) & ~(size_t)15;
+    // (9- / 10-bit lookup tables and a wave-uniform scalar bit reader measured slower)
+    hipLaunchKernelGGL((bzd_huff<8, true, MULTI>), dim3(D.count), dim3(64), sel_lds, st, D);
+    hipLaunchKernelGGL((bzd_tt<kTtThreads, MULTI>), dim3(slots), dim3(kTtThreads), 0, st, D);
+    // inverse-BWT walk, 512 threads per stream, the marker tables in LDS
+    // (large blocks, level 5 and up, keep them in global memory: LDS for ~2
+    // workgroups per CU at most)
+    const size_t wl = (size_t)D.mcap * 16;
+    if (wl <= 48 * 1024) hipLaunchKernelGGL((bzd_walk<512, true, MULTI>), dim3(slots), dim3(512), wl, st, D);
+    else hipLaunchKernelGGL((bzd_walk<512, false, MULTI>), dim3(slots), dim3(512), 0, st, D);
+    hipLaunchKernelGGL(bzd_rle1<MULTI>, dim3(slots), dim3(64), 0, st, D);
+    if (MULTI) hipLaunchKernelGGL(bzd_status, dim3((D.count + 255) / 256), dim3(256), 0, st, D);
+}
+
+int issue(const void* d_payload, const uint64_t* h_offs, uint32_t count, void* d_out, uint32_t out_stride,
+          uint32_t level, void* d_ws, size_t ws_bytes, uint32_t* h_lens, uint32_t* h_flags, hipStream_t st)
+{
     if (!d_payload || !h_offs || !count || !d_out || !out_stride || !d_ws) return LFM_HIP_EINVAL;
-    if (ws_bytes < lfm_hip_bunzip2_workspace_bytes(count, out_stride) || ((uintptr_t)d_payload & 3)) return LFM_HIP_EINVAL;
+    const uint32_t parts = level ? lfm::bz::max_parts(out_stride, level) : 1u;
+    if ((uint64_t)count * parts >= (1ull << 31)) return LFM_HIP_EINVAL;  // (slots are indexed in 32 bits)
+    Dec D{};
+    if (ws_bytes < layout((uint8_t*)d_ws, count, level ? level : level_of(out_stride), parts, D) ||
+        ((uintptr_t)d_payload & 3))
+        return LFM_HIP_EINVAL;
     if (!dcrc_ready) {
         for (uint32_t i = 0; i < 256; ++i) {
             uint32_t c = i << 24;
@@ -1194,48 +1422,23 @@ extern "C" int lfm_hip_bunzip2_issue(const void* d_payload, const uint64_t* h_of
             return LFM_HIP_ERUNTIME;
         crc_dev = dev;
     }
-    Dec D{};
     D.payload = (const uint8_t*)d_payload;
-    D.count = count;
-    D.cap = dec_cap(out_stride);
-    D.mcap = mark_cap(D.cap);
     D.out_stride = out_stride;
     D.out = (uint8_t*)d_out;
-    uint8_t* p = (uint8_t*)d_ws;
-    auto take = [&](size_t bytes) { uint8_t* r = p; p += al(bytes); return r; };
-    uint64_t* d_offs = (uint64_t*)take(((size_t)count + 1) * 8);
-    D.offs = d_offs;
-    D.ll = take((size_t)count * D.cap);
-    D.tt = (uint32_t*)take((size_t)count * D.cap * 4);
-    D.rle = D.ll;  // bzd_walk writes the text over ll (bzd_tt copied ll into tt)
-    D.mnext = (uint32_t*)take((size_t)count * D.mcap * 4);
-    D.mlen = (uint32_t*)take((size_t)count * D.mcap * 4);
-    D.mstart = (uint32_t*)take((size_t)count * D.mcap * 4);
-    D.mres = (uint32_t*)take((size_t)count * D.mcap * 4);
-    D.wkeep = take((size_t)count * D.mcap * kWalkKeep);
-    uint32_t** small[] = {&D.n, &D.orig, &D.crc, &D.flags, &D.out_len};
-    for (uint32_t** q : small) *q = (uint32_t*)take((size_t)count * 4 + 64);
-    (void)take((size_t)count * 4 + 64);
-    if (hipMemcpyAsync(d_offs, h_offs, ((size_t)count + 1) * 8, hipMemcpyHostToDevice, st) != hipSuccess)
+    if (hipMemcpyAsync((void*)D.offs, h_offs, ((size_t)count + 1) * 8, hipMemcpyHostToDevice, st) != hipSuccess)
         return LFM_HIP_ERUNTIME;
     D.sel_cap = std::min<uint32_t>(kMaxSel, (D.cap + 49) / 50 + 64);
-    const size_t sel_lds = ((D.sel_cap + 7) / 8 * 4 + 15) & ~(size_t)15;
-    // (9- / 10-bit lookup tables and a wave-uniform scalar bit reader measured slower)
-    hipLaunchKernelGGL((bzd_huff<8, true>), dim3(count), dim3(64), sel_lds, st, D);
-    hipLaunchKernelGGL(bzd_tt<kTtThreads>, dim3(count), dim3(kTtThreads), 0, st, D);
-    // inverse-BWT walk, 512 threads per stream, the marker tables in LDS
-    // (large blocks, level 5 and up, keep them in global memory: LDS for ~2
-    // workgroups per CU at most)
-    const size_t wl = (size_t)D.mcap * 16;
-    if (wl <= 48 * 1024) hipLaunchKernelGGL((bzd_walk<512, true>), dim3(count), dim3(512), wl, st, D);
-    else hipLaunchKernelGGL((bzd_walk<512, false>), dim3(count), dim3(512), 0, st, D);
-    hipLaunchKernelGGL(bzd_rle1, dim3(count), dim3(64), 0, st, D);
+    // with one slot per stream the single-block kernels, whichever entry asked
+    if (parts > 1) launch<true>(D, count * parts, st);
+    else launch<false>(D, count, st);
     if (hipGetLastError() != hipSuccess) return LFM_HIP_ERUNTIME;
-    if (hipMemcpyAsync(h_lens, D.out_len, (size_t)count * 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
-        hipMemcpyAsync(h_flags, D.flags, (size_t)count * 4, hipMemcpyDeviceToHost, st) != hipSuccess)
+    if (hipMemcpyAsync(h_lens, D.s_len, (size_t)count * 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
+        hipMemcpyAsync(h_flags, D.s_flag, (size_t)count * 4, hipMemcpyDeviceToHost, st) != hipSuccess)
         return LFM_HIP_ERUNTIME;
     return LFM_HIP_OK;
 }
+
+} // namespace
 
 // ------------------------------------------------------------ block scatter --
 namespace lfm {

@@ -22,4 +22,15 @@ constexpr int kGSize = 50;  // symbols per Huffman selector (compress.c BZ_G_SIZ
 // selectors of a stream
 inline uint32_t sel_cap(uint32_t block_bytes) { return (uint32_t)align_up(rle_cap(block_bytes) / kGSize + 8, 64); }
 
+// bzip2 blocks libbzip2 can cut a block of block_bytes into at `level` (1..9):
+// the RLE1 text is at most 5/4 of the block, and every part but the last holds
+// at least nblockMAX = 100000 * level - 19 bytes of it.  The slots a stream
+// owns in the encoder's (lfm_bzip2.hip) and the decoder's (lfm_bunzip2.hip)
+// multi-block workspaces.
+inline uint32_t max_parts(uint32_t block_bytes, uint32_t level)
+{
+    const uint64_t worst = (uint64_t)block_bytes + block_bytes / 4 + 1;
+    return (uint32_t)(worst / (100000u * level - 19u)) + 1u;
+}
+
 } // namespace lfm::bz

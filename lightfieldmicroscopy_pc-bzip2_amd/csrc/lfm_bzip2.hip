@@ -65,7 +65,7 @@
 #include <mutex>
 #include <type_traits>
 #include <vector>
-#include "lfm_bz_caps.h"  // rle_cap, out_cap, sel_cap, kGSize, align_up
+#include "lfm_bz_caps.h"  // rle_cap, out_cap, sel_cap, kGSize, align_up, max_parts
 #include "lfm_hip.h"
 
 #ifndef LFM_BWT_FORCE_FULL
@@ -3673,15 +3673,6 @@ struct BwtStats {
     uint32_t first_ties = 0;  // tied slots after the chunk sorts
     uint32_t left_runs = 0;   // runs tie_runs_direct left
 };
-
-// bzip2 blocks libbzip2 can cut a block of block_bytes into at `level`: the
-// RLE1 text is at most 5/4 of the block, and every part but the last holds at
-// least nblockMAX bytes of it
-uint32_t max_parts(uint32_t block_bytes, uint32_t level)
-{
-    const uint64_t worst = (uint64_t)block_bytes + block_bytes / 4 + 1;
-    return (uint32_t)(worst / (100000u * level - 19u)) + 1u;
-}
 
 // The workspace, described once: every buffer in order, 256-byte aligned.
 // With base == nullptr this only sums (lfm_hip_bzip2_workspace_bytes); with

@@ -175,6 +175,12 @@ struct Timeline {
     }
 };
 
+std::atomic<int>& bunzip2_multiblock_flag()
+{
+    static std::atomic<int> on{env_int("LFM_BUNZIP2_MULTIBLOCK", 1) != 0 ? 1 : 0};
+    return on;
+}
+
 // How a payload is cut into chunks, computed once from header, grid and
 // switches.
 // chunks: whole slabs, at least two and about LFM_DECODE_CHUNK_BLOCKS
@@ -192,8 +198,19 @@ struct DecodePlan {
     // (a chunk's slabs lie in at most spc volumes)
     uint64_t us_per;
     size_t ws;                    // a slot's workspace
+    // streams of several bzip2 blocks on the device (bunzip2_multiblock(), read
+    // once per decode): the bzip2 level the writer chose for the nominal block
+    // (klb_imageIO.cpp:108), which sizes a stream's slots; 0: the single-block
+    // entries, such streams go to the host library
+    uint32_t level;
+    size_t ws_bytes(uint32_t n, uint32_t block_bytes) const
+    {
+        return level ? lfm_hip_bunzip2_workspace_bytes_multi(n, block_bytes, level)
+                     : lfm_hip_bunzip2_workspace_bytes(n, block_bytes);
+    }
     DecodePlan(const BlockGrid& g, uint32_t block_bytes)
     {
+        level = bunzip2_multiblock() ? std::min<uint32_t>(9, std::max<uint32_t>(1, (block_bytes + 99999) / 100000)) : 0;
         const uint64_t nb = g.nblocks, slab = g.nb[0] * g.nb[1];
         nslabs = nb / slab;
         nbz = g.nb[2];
@@ -206,12 +223,12 @@ struct DecodePlan {
             const uint64_t want = std::max<uint64_t>(slots, (nb + (uint64_t)target - 1) / (uint64_t)target);
             spc = std::max<uint64_t>(1, (nslabs + want - 1) / want);
         }
-        const size_t per = lfm_hip_bunzip2_workspace_bytes(1, block_bytes) + block_bytes;
+        const size_t per = ws_bytes(1, block_bytes) + block_bytes;
         const size_t budget = (size_t)env_int("LFM_BUNZIP2_GPU_BUDGET_MB", 16 * 1024) << 20;
         spc = std::max<uint64_t>(1, std::min<uint64_t>(spc, budget / slots / per / slab));
         batch = spc * slab;
         nch = (nslabs + spc - 1) / spc;
-        ws = lfm_hip_bunzip2_workspace_bytes((uint32_t)batch, block_bytes);
+        ws = ws_bytes((uint32_t)batch, block_bytes);
         nslot = (int)std::min<uint64_t>(nch, (uint64_t)slots);
         us_per = spc + 1;
     }
@@ -474,6 +491,9 @@ bool decode_job_buffers(DecodeJob& J, size_t pay_bytes, size_t img_bytes, uint32
 }
 } // namespace
 
+int bunzip2_multiblock() { return bunzip2_multiblock_flag().load(); }
+int set_bunzip2_multiblock(int on) { return bunzip2_multiblock_flag().exchange(on ? 1 : 0); }
+
 // GPU decode of a BZIP2 payload (lfm_bunzip2.hip), pipelined over chunks of
 // whole block slabs (the blocks of one z-block row of one volume, so a chunk's
 // pixels are a contiguous run of frames of the image): per chunk the payload
@@ -577,8 +597,13 @@ static int gpu_decode(const uint8_t* payload, size_t len, const klb_image_header
         t_up += ms_since(t0);
         tl.mark("uploaded", c);
         if (c == 0 && prefault_mode == 2 && !dd) start_prefault();
-        if (lfm_hip_bunzip2_issue(J.d_pay, offs.data() + b0, (uint32_t)cnt, J.d_blk[q], block_bytes, J.d_ws[q], P.ws,
-                                  J.hs[q], J.hs[q] + P.batch, DB.st[q]) != LFM_HIP_OK) {
+        const int irc = P.level ? lfm_hip_bunzip2_issue_multi(J.d_pay, offs.data() + b0, (uint32_t)cnt, J.d_blk[q],
+                                                              block_bytes, P.level, J.d_ws[q], P.ws, J.hs[q],
+                                                              J.hs[q] + P.batch, DB.st[q])
+                                : lfm_hip_bunzip2_issue(J.d_pay, offs.data() + b0, (uint32_t)cnt, J.d_blk[q],
+                                                        block_bytes, J.d_ws[q], P.ws, J.hs[q], J.hs[q] + P.batch,
+                                                        DB.st[q]);
+        if (irc != LFM_HIP_OK) {
             rc = 3;
             break;
         }

@@ -141,6 +141,12 @@ int bzip2_level(const klb_image_header& h);
 // setter returns the previous value
 int bzip2_multiblock();
 int set_bzip2_multiblock(int on);
+// the reader's side of the same: GPU decode of streams of several bzip2 blocks
+// (1, the default; env LFM_BUNZIP2_MULTIBLOCK) or their decode by the host
+// library (0); read once by every decode as it starts, the setter returns the
+// previous value
+int bunzip2_multiblock();
+int set_bunzip2_multiblock(int on);
 // multi-threaded memcpy (1 MiB pieces)
 void par_memcpy(void* dst, const void* src, size_t n, int threads);
 

@@ -41,6 +41,7 @@ EXPORTS = [
     "lfm_set_decode_devices", "lfm_get_decode_devices", "lfm_default_decode_devices", "lfm_release_decoders",
     "lfm_decode_shard_plan", "lfm_decode_memory_multi", "lfm_decode_memory_multi_device",
     "lfm_set_bzip2_multiblock", "lfm_get_bzip2_multiblock", "lfm_encoder_stream_counts",
+    "lfm_set_bunzip2_multiblock", "lfm_get_bunzip2_multiblock",
     # lfm_hip.h
     "lfm_hip_predict", "lfm_hip_unpredict", "lfm_hip_unpredict_async", "lfm_hip_unpredict_check",
     "lfm_hip_unpredict_path",
@@ -49,6 +50,8 @@ EXPORTS = [
     "lfm_hip_bzip2_blocks", "lfm_hip_bzip2_last_stage_ms", "lfm_hip_bunzip2_workspace_bytes", "lfm_hip_bunzip2_blocks", "lfm_hip_scatter_blocks",
     "lfm_hip_crop_region", "lfm_hip_bzip2_workspace_bytes_multi", "lfm_hip_bzip2_max_count_multi",
     "lfm_hip_bzip2_blocks_multi", "lfm_hip_bzip2_last_blocks",
+    "lfm_hip_bunzip2_max_parts", "lfm_hip_bunzip2_workspace_bytes_multi", "lfm_hip_bunzip2_blocks_multi",
+    "lfm_hip_bunzip2_issue_multi",
 ]
 
 
@@ -193,6 +196,14 @@ def lib():
     L.lfm_hip_bunzip2_workspace_bytes.restype = ctypes.c_size_t
     L.lfm_hip_bunzip2_blocks.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64), ctypes.c_uint32, vp, ctypes.c_uint32,
                                          vp, ctypes.c_size_t, u32p, u32p, vp]
+    L.lfm_hip_bunzip2_max_parts.argtypes = [ctypes.c_uint32] * 2
+    L.lfm_hip_bunzip2_max_parts.restype = ctypes.c_uint32
+    L.lfm_hip_bunzip2_workspace_bytes_multi.argtypes = [ctypes.c_uint32] * 3
+    L.lfm_hip_bunzip2_workspace_bytes_multi.restype = ctypes.c_size_t
+    L.lfm_hip_bunzip2_blocks_multi.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64), ctypes.c_uint32, vp,
+                                               ctypes.c_uint32, ctypes.c_uint32, vp, ctypes.c_size_t, u32p, u32p, vp]
+    L.lfm_set_bunzip2_multiblock.argtypes = [ctypes.c_int]
+    L.lfm_get_bunzip2_multiblock.argtypes = []
     L.lfm_hip_scatter_blocks.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, u32p, u32p,
                                          ctypes.c_uint32, vp, vp]
     L.lfm_hip_select_workspace_bytes.restype = ctypes.c_size_t
@@ -961,23 +972,54 @@ def bzip2_device(d_img, dims, block, bpp, level=None, first=0, count=None, strea
     return out, list(flags)
 
 
-def bunzip2_device(streams, out_stride, device="cuda", stream=None):
-    """GPU bzip2 decode of single-block streams (bytes objects).  Returns
-    ([bytes per stream, or None where the device flagged it for the host
-    library], flags): flag 1 = host library, 2 = block CRC mismatch."""
+def set_bunzip2_multiblock(on):
+    """GPU decode of streams of several bzip2 blocks on (default) or off (such
+    streams are decoded by the host library); returns the previous setting."""
+    return bool(lib().lfm_set_bunzip2_multiblock(1 if on else 0))
+
+
+def get_bunzip2_multiblock():
+    return bool(lib().lfm_get_bunzip2_multiblock())
+
+
+def bunzip2_max_parts(out_stride, level):
+    """bzip2 blocks a stream of at most out_stride decoded bytes can hold at
+    `level`: the slots it owns in bunzip2_device(..., multi=True).  0 for a
+    level outside 1..9.  No GPU."""
+    return int(lib().lfm_hip_bunzip2_max_parts(out_stride, level))
+
+
+def bunzip2_device(streams, out_stride, device="cuda", stream=None, multi=False, level=None):
+    """GPU bzip2 decode of streams (bytes objects).  Returns ([bytes per
+    stream, or None where the device flagged it for the host library],
+    flags): flag 1 = host library, 2 = block CRC mismatch.
+    multi=False: lfm_hip_bunzip2_blocks, single-block streams only.
+    multi=True: lfm_hip_bunzip2_blocks_multi, which also decodes streams of up
+    to bunzip2_max_parts(out_stride, level) bzip2 blocks of `level` (default:
+    the writer's, min(9, ceil(out_stride / 100000)))."""
     count = len(streams)
     offs = np.zeros(count + 1, dtype=np.uint64)
     offs[1:] = np.cumsum([len(x) for x in streams])
     blob = b"".join(streams) + bytes(64)
     d_pay = torch.frombuffer(bytearray(blob), dtype=torch.uint8).to(device)
-    ws_bytes = lib().lfm_hip_bunzip2_workspace_bytes(count, out_stride)
+    level = max(1, min(9, -(-out_stride // 100000))) if level is None else level
+    if multi:
+        ws_bytes = lib().lfm_hip_bunzip2_workspace_bytes_multi(count, out_stride, level)
+    else:
+        ws_bytes = lib().lfm_hip_bunzip2_workspace_bytes(count, out_stride)
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=device)
     out = torch.empty(count * out_stride, dtype=torch.uint8, device=device)
     lens = (ctypes.c_uint32 * count)()
     flags = (ctypes.c_uint32 * count)()
-    _check(lib().lfm_hip_bunzip2_blocks(d_pay.data_ptr(), offs.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), count,
-                                        out.data_ptr(), out_stride, ws.data_ptr(), ws_bytes, lens, flags,
-                                        _stream(stream)), "lfm_hip_bunzip2_blocks")
+    p_offs = offs.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))
+    if multi:
+        _check(lib().lfm_hip_bunzip2_blocks_multi(d_pay.data_ptr(), p_offs, count, out.data_ptr(), out_stride, level,
+                                                  ws.data_ptr(), ws_bytes, lens, flags, _stream(stream)),
+               "lfm_hip_bunzip2_blocks_multi")
+    else:
+        _check(lib().lfm_hip_bunzip2_blocks(d_pay.data_ptr(), p_offs, count, out.data_ptr(), out_stride,
+                                            ws.data_ptr(), ws_bytes, lens, flags, _stream(stream)),
+               "lfm_hip_bunzip2_blocks")
     host = out.cpu().numpy()
     res = [None if flags[i] else host[i * out_stride:i * out_stride + lens[i]].tobytes() for i in range(count)]
     return res, list(flags)
