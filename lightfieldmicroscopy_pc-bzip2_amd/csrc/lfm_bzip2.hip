@@ -142,9 +142,8 @@ struct Batch {
     uint32_t* nsub;          // rotations sorted per stream (the A or B rotations, or all of them)
     uint32_t* bwt_mode;      // per stream: kModeSortA / kModeSortB / kModeFull
     uint32_t* abcnt;         // per stream: A rotations per first byte [256], then B rotations [256]
-    uint32_t* itab;          // per stream: q0, p0, p1, s0 [256] each (bwt_bucket, for bwt_place_sorted)
-    uint32_t* sfin;          // the final order of every rotation (bwt_place_sorted / bwt_induce)
-    uint2* ent;              // bwt_induce's entries per final position (the keys_a area, free after the sorts)
+    uint32_t* itab;          // per stream: tq, cs, cl, s0 [256] each (bwt_bucket, for bwt_place_sorted / bwt_induce)
+    uint2* ent;              // bwt_induce's entries per compact scan index (the keys_a area, free after the sorts)
     uint32_t it_full;        // sort every rotation (no induction): the fallback for ties that need doubling
     // streams of several bzip2 blocks (lfm_hip_bzip2_blocks_multi): a stream
     // owns `parts` consecutive slots, one per bzip2 block ("part") libbzip2
@@ -909,8 +908,9 @@ __global__ __launch_bounds__(kBucketThreads) __attribute__((amdgpu_waves_per_eu(
     __shared__ uint32_t ccount[4], cbase[4];
     __shared__ uint32_t sinuse[8];                  // bytes present in the RLE1 text (the stream's inUse map)
     __shared__ uint32_t cnt_u[256], cnt_s[256];     // unsorted / sorted rotations per first byte
+    __shared__ uint32_t cnt_l[256];                 // unsorted rotations that induce ("live"), per first byte
     __shared__ uint32_t undecided, n_unsorted;
-    __shared__ uint32_t tsum[8];
+    __shared__ uint32_t tsum[12];
     const uint32_t s = blockIdx.x, t = threadIdx.x, lane = t & 63, wave = t >> 6;
     if (B.flags[s] & kFlagHost) return;
     const uint32_t n = B.n[s];
@@ -924,13 +924,13 @@ __global__ __launch_bounds__(kBucketThreads) __attribute__((amdgpu_waves_per_eu(
     uint32_t mode = B.it_full ? kModeFull : kModeSortA;
     for (;;) {
         for (uint32_t b = t; b < kBuckets; b += kBucketThreads) hist[b] = 0;
-        if (t < 256) cnt_u[t] = cnt_s[t] = 0;
+        if (t < 256) cnt_u[t] = cnt_s[t] = cnt_l[t] = 0;
         if (t == 0) undecided = n_unsorted = 0;
         __syncthreads();
         // unsorted rotations starting with byte 0 (the high bytes of small
         // 16-bit symbols: about half of all rotations) are counted in a
         // register -- their LDS atomics all hit one word and serialise
-        uint32_t u_zero = 0;
+        uint32_t u_zero = 0, l_zero = 0;
         // sorted rotations in buckets a << (BITS - 8) for a < 4 (a small low
         // byte, then a zero high byte: the hottest buckets) likewise, in
         // 16-bit register fields
@@ -956,11 +956,24 @@ __global__ __launch_bounds__(kBucketThreads) __attribute__((amdgpu_waves_per_eu(
                         atomicAdd(&hist[bkt_slot<BITS>(key)], 1u);
                     }
                 }
-                else if (a == 0u) ++u_zero;
-                else atomicAdd(&cnt_u[a], 1u);
+                else {
+                    // an unsorted rotation k induces k - 1 ("live") when k - 1
+                    // is unsorted too: by bwt_induce's own byte rule, T[k-1]
+                    // against T[k] in the direction of the mode's scan
+                    const uint32_t pb = tile[kTOff + k - 1];
+                    const bool live = mode == kModeSortA ? pb <= a : pb >= a;
+                    if (a == 0u) {
+                        ++u_zero;
+                        l_zero += live;
+                    } else {
+                        atomicAdd(&cnt_u[a], 1u);
+                        if (live) atomicAdd(&cnt_l[a], 1u);
+                    }
+                }
             }
         }
         if (u_zero) atomicAdd(&cnt_u[0], u_zero);
+        if (l_zero) atomicAdd(&cnt_l[0], l_zero);
 #pragma unroll
         for (uint32_t h = 0; h < 4; ++h) {
             const uint32_t c = ((h < 2u ? hot01 : hot23) >> (16u * (h & 1u))) & 0xFFFFu;
@@ -1044,28 +1057,34 @@ __global__ __launch_bounds__(kBucketThreads) __attribute__((amdgpu_waves_per_eu(
         });
     }
     if (t < 8) B.inuse[s * 8 + t] = sinuse[t];  // (written after the scan's barrier)
-    {  // A / B rotations per first byte for bwt_induce, and bwt_place_sorted's
-       // tables: q-order start of bucket c (q0), its placed part (p0 .. p1)
-       // and the first sa slot of its sorted rotations (s0)
-        uint32_t na = 0, nb = 0, ns = 0, x = 0, y = 0;
+    {  // A / B rotations per first byte for bwt_induce, and the tables of
+       // bwt_place_sorted and bwt_induce (see "induction" below): the final
+       // position of bucket c's first sorted rotation (tq), the first sa slot
+       // of its sorted rotations (s0), and, by scan bucket u, the compact
+       // scan index of its first live slot (cs) and its live count (cl)
+        uint32_t na = 0, nb = 0, ns = 0, nl = 0, x = 0, y = 0, z = 0;
         if (t < 256) {
             na = mode == kModeSortA ? cnt_s[t] : cnt_u[t];
             nb = mode == kModeSortA ? cnt_u[t] : cnt_s[t];
             ns = mode == kModeSortA ? na : nb;  // (kModeFull: all in the B counts)
+            nl = mode == kModeFull ? 0u : cnt_l[t];
             B.abcnt[(size_t)s * 512 + t] = na;
             B.abcnt[(size_t)s * 512 + 256 + t] = nb;
             x = na + nb;
             y = ns;
+            z = nl + ns;
             for (int d = 1; d < 64; d <<= 1) {
-                const uint32_t a = __shfl_up(x, d), b = __shfl_up(y, d);
+                const uint32_t a = __shfl_up(x, d), b = __shfl_up(y, d), c = __shfl_up(z, d);
                 if ((int)lane >= d) {
                     x += a;
                     y += b;
+                    z += c;
                 }
             }
             if (lane == 63) {
                 tsum[wave] = x;
                 tsum[4 + wave] = y;
+                tsum[8 + wave] = z;
             }
         }
         __syncthreads();
@@ -1073,12 +1092,16 @@ __global__ __launch_bounds__(kBucketThreads) __attribute__((amdgpu_waves_per_eu(
             for (uint32_t w = 0; w < wave; ++w) {
                 x += tsum[w];
                 y += tsum[4 + w];
+                z += tsum[8 + w];
             }
+            const uint32_t nc = tsum[8] + tsum[9] + tsum[10] + tsum[11];  // the compact scan's length
             const uint32_t qs = x - na - nb;
+            const bool rev = mode == kModeSortA;  // the scan runs right to left: scan bucket u = 255 - c
+            const uint32_t u = rev ? 255u - t : t;
             uint32_t* it = B.itab + (size_t)s * 1024;
-            it[t] = qs;
-            it[256 + t] = mode == kModeSortA ? qs + na : qs;
-            it[512 + t] = mode == kModeSortA ? qs + na + nb : (mode == kModeSortB ? qs + na : qs);
+            it[t] = mode == kModeSortB ? qs + na : qs;
+            it[256 + u] = rev ? nc - z : z - (nl + ns);
+            it[512 + u] = nl;
             it[768 + t] = y - ns;
         }
     }
@@ -1713,42 +1736,64 @@ __device__ __forceinline__ void make_u2s(const Batch& B, uint32_t s, uint8_t* u2
 // induces i - 1 when b' = T[i-1]' > u, or b' == u and i was placed itself;
 // i - 1 takes the next free slot of bucket b''s placed part (head[b']).
 //
-// Entries: lo = i | nprev << 20 | placed << 23 | T[i-1] << 24 (the sort
-// value's layout, bits 20-23 free since n < 2^20), hi = T[i-2] | T[i-3] << 8
-// | T[i-4] << 16 | T[i] << 24: nprev of the three bytes before T[i-1] are
-// valid (3 for a sorted rotation, one fewer per induction: a longer chain of
-// placed rotations reads the text), and T[i] is the rotation's bucket.
-// bwt_place_sorted writes the sorted entries to their final positions in
-// `ent` and kIndPend to every position still to place; bwt_induce then
-// reads nothing else, and writes every position's sort value to sfin.
+// The output is ll[]: at every final position the symbol of the byte before
+// its rotation, and origPtr, the position of rotation 0.  Whoever places a
+// rotation holds that byte and writes the symbol there: bwt_place_sorted for
+// the sorted rotations, bwt_induce for each rotation it induces.
+//
+// A placed rotation p induces in its turn only when p - 1 is placed too, by
+// the rule above when T[p-1]' >= T[p]': it is "live".  The others are dead:
+// nothing reads them again (on 16-bit little-endian symbols the placed
+// rotations start at the high bytes and 98 % of them are dead), so the scan
+// does not visit them.  It runs over a compact index: for each bucket u in
+// scan order cl[u] slots for its live rotations, from cs[u], then its sorted
+// rotations in scan order; bwt_bucket counts cl[] with the same byte rule.
+// Beside head[b'] the scan keeps chead[b'], the next free live slot.
+//
+// Entries (`ent`, by compact index): lo = i | nprev << 20 | placed << 23 |
+// T[i-1] << 24 (the sort value's layout, bits 20-23 free since n < 2^20),
+// hi = T[i-2] | T[i-3] << 8 | T[i-4] << 16 | T[i] << 24: nprev of the three
+// bytes before T[i-1] are valid (3 for a sorted rotation, one fewer per
+// induction: a longer chain of placed rotations reads the text), and T[i] is
+// the rotation's bucket.  bwt_place_sorted writes the sorted entries and
+// kIndPend into the live slots; bwt_induce fills those as it goes.
+//
+// itab (bwt_bucket), 256 words each: tq[c] the final position of bucket c's
+// first sorted rotation, cs[u], cl[u], and s0[c] the sa slot of bucket c's
+// first sorted rotation.
 constexpr uint32_t kIndPend = 0xFFFFFFFFu;  // never an entry: nprev <= 3
 constexpr uint32_t kIndIdx = 0xFFFFFu;      // n < nblock_max < 2^20
 constexpr uint32_t kIndPlaced = 1u << 23;
 constexpr uint32_t kPlaceChunk = 2048;  // (1 024, 4 096, 8 192 equal or slower end to end)  // sorted slots / positions per bwt_place_sorted workgroup
 
-// One workgroup per kPlaceChunk sorted slots and final positions of a
+// One workgroup per kPlaceChunk sorted slots and compact scan indices of a
 // stream, the chunks of a stream consecutive on one XCD (workgroup w runs on
 // XCD w % 8): the text reads are random inside the stream, so a stream's text
 // should stay in one L2 while its chunks run.
 __global__ __launch_bounds__(256) void bwt_place_sorted(Batch B, uint32_t chunks)
 {
-    __shared__ uint32_t q0[256], p0[256], p1[256], s0[256];
+    __shared__ uint32_t tq[256], cs[256], cl[256], s0[256];
+    __shared__ uint32_t cb[256];  // compact index of bucket c's first sorted rotation (kModeSortA: the ranks count down from it)
     __shared__ uint8_t u2s[256];
     const uint32_t t = threadIdx.x, k = blockIdx.x >> 3;
     const uint32_t s = (blockIdx.x & 7u) + 8u * (k / chunks), base = (k % chunks) * kPlaceChunk;
     if (s >= B.nstreams || (B.flags[s] & kFlagHost)) return;
     const uint32_t n = B.n[s], ns = B.nsub[s], mode = B.bwt_mode[s];
     if (base >= n) return;
-    if (mode == kModeFull && t < 64) {
+    const bool rev = mode == kModeSortA;
+    if (t < 64) {
         uint32_t nin;
         make_u2s(B, s, u2s, t, &nin);
     }
     {
         const uint32_t* it = B.itab + (size_t)s * 1024;
-        q0[t] = it[t];
-        p0[t] = it[256 + t];
-        p1[t] = it[512 + t];
+        const uint32_t u = rev ? 255u - t : t;
+        tq[t] = it[t];
+        cs[t] = it[256 + t];
+        cl[t] = it[512 + t];
         s0[t] = it[768 + t];
+        // (an empty sorted part: never used)
+        cb[t] = it[256 + u] + it[512 + u] + (rev ? B.abcnt[(size_t)s * 512 + t] - 1u : 0u);
     }
     __syncthreads();
     const size_t o = (size_t)s * B.cap;
@@ -1785,42 +1830,46 @@ __global__ __launch_bounds__(256) void bwt_place_sorted(Batch B, uint32_t chunks
             for (uint32_t r = 1; r <= 4; ++r) x |= (uint32_t)T[(i + 4 * n - r) % n] << (32 - 8 * r);
             c = T[i];
         }
-        const uint32_t qq = (mode == kModeSortA ? q0[c] : p1[c]) + (j - s0[c]);
-        if (mode == kModeFull) {  // the final order already: the symbol, and origPtr at rotation 0
-            LL[qq] = u2s[v[q] >> 24];
-            if (i == 0) B.orig_ptr[s] = qq;
-        }
-        else
-            E[qq] = make_uint2(v[q] | (3u << 20),
-                               ((x >> 16) & 0xFFu) | (((x >> 8) & 0xFFu) << 8) | ((x & 0xFFu) << 16) | (c << 24));
+        // its final position is known: the symbol, and origPtr at rotation 0
+        const uint32_t r = j - s0[c], qq = tq[c] + r;
+        LL[qq] = u2s[v[q] >> 24];
+        if (i == 0) B.orig_ptr[s] = qq;
+        if (mode != kModeFull)
+            E[rev ? cb[c] - r : cb[c] + r] =
+                make_uint2(v[q] | (3u << 20),
+                           ((x >> 16) & 0xFFu) | (((x >> 8) & 0xFFu) << 8) | ((x & 0xFFu) << 16) | (c << 24));
     }
-    // the positions [base, base + kPlaceChunk) still to place: the buckets
-    // overlapping the range, from the last one starting at or before base
-    const uint32_t end = min(n, base + kPlaceChunk);
+    if (mode == kModeFull) return;
+    // the live slots among the compact indices [base, base + kPlaceChunk): of
+    // the buckets overlapping the range, from the last one starting at or
+    // before base (every live range lies below the compact length)
+    const uint32_t end = base + kPlaceChunk;
     uint32_t lo = 0, hi = 255;
     while (lo < hi) {
         const uint32_t mid = (lo + hi + 1) >> 1;
-        if (q0[mid] <= base) lo = mid;
+        if (cs[mid] <= base) lo = mid;
         else hi = mid - 1;
     }
-    for (uint32_t c = lo; c < 256 && q0[c] < end; ++c)
-        for (uint32_t q = max(p0[c], base) + t; q < min(p1[c], end); q += 256) E[q] = make_uint2(kIndPend, 0u);
+    for (uint32_t u = lo; u < 256 && cs[u] < end; ++u)
+        for (uint32_t q = max(cs[u], base) + t; q < min(cs[u] + cl[u], end); q += 256) E[q] = make_uint2(kIndPend, 0u);
 }
 
-// bwt_induce: one wave per stream scans in scan order, in blocks of
-// kIndSlices slices of 64 positions through an LDS ring of two blocks:
+// bwt_induce: one wave per stream scans the compact index, in blocks of
+// kIndSlices slices of 64 indices through an LDS ring of two blocks: live
 // entries placed into the current or the next block go to the ring, those
 // further ahead to `ent`; while a block is scanned the next block's entries
 // are loaded (LDS-DMA, 16 bytes per lane) and written into the ring after the
-// scan (kIndPend = not placed yet).  The final values of a block collect in
-// LDS and leave in 16-byte stores: the wave's memory instructions, not its
-// arithmetic, bound the scan (each store stays outstanding for thousands of
-// cycles with every CU storing), so there are few and wide ones.  The
-// inducing lanes of a slice are ranked per b' with one ballot per distinct b'
-// (the predecessors of a run of sorted rotations take few distinct bytes), so
-// the slots follow the scan order; an entry still pending when its slice is
-// scanned is placed by an earlier lane of the same slice: the step then runs
-// in rounds up to its first pending lane.
+// scan (kIndPend = not placed yet).  Every induced rotation's symbol goes to
+// ll[] at its final position (head[b'] + rank: the lanes of one b' store
+// consecutive bytes); only a live one also gets an entry, at chead[b'] + its
+// rank among the live ones.  The inducing lanes of a slice are ranked per b'
+// with one ballot per distinct b' (the predecessors of a run of sorted
+// rotations take few distinct bytes), so the slots follow the scan order; an
+// entry still pending when its slice is scanned is placed by an earlier lane
+// of the same slice: the step then runs in rounds up to its first pending
+// lane.  The counts are checked as the scan goes (no slot past its bucket's
+// part, no live slot left pending) and at its end (every head at the end of
+// its part): a stream that fails goes to the host library.
 constexpr uint32_t kIndSlices = 8;
 constexpr uint32_t kIndBlock = 64 * kIndSlices;
 constexpr int kIndStepSlices = 4;  // slices scanned together (2 and 8 measured slower in the pipeline)
@@ -1838,21 +1887,14 @@ __device__ __forceinline__ void glds16(const void* g, const void* lds)
     asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off sc1" ::"s"(m0), "v"(g) : "memory", "m0");
 }
 
-__device__ __forceinline__ void glds4(const uint32_t* g, const void* lds)  // 4 bytes per lane
-{
-    const uint32_t m0 = __builtin_amdgcn_readfirstlane(
-        (uint32_t)(size_t)(const __attribute__((address_space(3))) void*)lds);
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dword %1, off sc1" ::"s"(m0), "v"(g) : "memory", "m0");
-}
-
 __device__ __forceinline__ void vm_drain() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 
 __global__ __launch_bounds__(64) void bwt_induce(Batch B)
 {
-    __shared__ uint32_t head[256];            // next free scan position of bucket u's placed part
+    __shared__ uint32_t head[256], hlim[256];    // next free scan position of bucket u's placed part, and its end
+    __shared__ uint32_t chead[256], clim[256];   // next free compact index of bucket u's live slots, and their end
     __shared__ uint2 ring[kIndRing];
-    __shared__ __attribute__((aligned(16))) uint2 stg[kIndBlock + 32];      // the next block's entries, in q order
-    __shared__ __attribute__((aligned(16))) uint8_t fin[kIndBlock + 32];  // the block's symbols, in q order
+    __shared__ __attribute__((aligned(16))) uint2 stg[kIndBlock];  // the next block's entries
     __shared__ uint8_t u2s[256];
     const uint32_t s = blockIdx.x, lane = threadIdx.x;
     if (B.flags[s] & kFlagHost) return;
@@ -1868,13 +1910,21 @@ __global__ __launch_bounds__(64) void bwt_induce(Batch B)
     uint32_t nin;
     make_u2s(B, s, u2s, lane, &nin);
     const bool u2s_id = nin == 256;  // every byte in use: the map is the identity
+    const uint32_t* it = B.itab + (size_t)s * 1024;
+    // the compact scan's length: the end of the last bucket's sorted part
+    const uint32_t nc = min(n, it[256 + 255] + it[512 + 255] + B.abcnt[(size_t)s * 512 + (rev ? 0u : 256u) + (255u ^ mir)]);
     {  // head[u] = scan-order start of bucket u (its placed part comes first)
-        uint32_t nt[4], l = 0;
+        uint32_t nt[4], np[4], l = 0;
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-            const uint32_t c = (4 * lane + q) ^ mir;
-            nt[q] = B.abcnt[(size_t)s * 512 + c] + B.abcnt[(size_t)s * 512 + 256 + c];
+            const uint32_t u = 4 * lane + q, c = u ^ mir;
+            const uint32_t na = B.abcnt[(size_t)s * 512 + c], nb = B.abcnt[(size_t)s * 512 + 256 + c];
+            nt[q] = na + nb;
+            np[q] = rev ? nb : na;
             l += nt[q];
+            const uint32_t c0 = it[256 + u], c1 = c0 + it[512 + u];
+            chead[u] = c0;
+            clim[u] = min(c1, nc);
         }
         uint32_t x = l;
         for (int d = 1; d < 64; d <<= 1) {
@@ -1885,91 +1935,53 @@ __global__ __launch_bounds__(64) void bwt_induce(Batch B)
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             head[4 * lane + q] = x;
+            hlim[4 * lane + q] = x + np[q];
             x += nt[q];
         }
     }
     for (uint32_t i = lane; i < kIndRing; i += 64) ring[i].x = kIndPend;
-    // position in `ent` / ll of scan position v.  A block [vb, vb + kIndBlock)
-    // covers q in [qwin(vb), qwin(vb) + kIndBlock); stg holds it from q =
-    // qwin & ~1, fin from q = qwin & ~15 (16-byte aligned transfers)
+    __syncthreads();
+    // `ent` is in scan order; ll[] is in final order: position n - 1 - v for
+    // scan position v of a right-to-left scan
     const uint32_t qa = rev ? n - 1 : 0u;
     auto qof = [&](uint32_t v) { return rev ? qa - v : v; };
-    auto qwin = [&](uint32_t vb) { return rev ? (int)n - (int)kIndBlock - (int)vb : (int)vb; };
-    // slot of the block's t-th position in a buffer starting d before qwin
-    auto wof = [&](uint32_t t, int d) { return rev ? (uint32_t)d + kIndBlock - 1 - t : t; };
-    const int qmax = (int)B.cap - 2;
+    const uint32_t qmax = B.cap - 2;
     auto issue = [&](uint32_t vb) {  // the block at vb into stg (clamped: every lane loads)
-        const int qw = qwin(vb), qs = qw & ~1;
 #pragma unroll
-        for (uint32_t j = 0; j < kIndBlock / 128; ++j) {
-            const int q = min(max(qs + (int)(128 * j + 2 * lane), 0), qmax);
-            glds16(E + q, &stg[128 * j]);
-        }
-        if (qw & 1) {  // the block's last slot: entry qs + kIndBlock, one dword per lane 0 and 1
-            const int q = min(max(qs + (int)kIndBlock, 0), qmax);
-            glds4((const uint32_t*)(E + q) + min(lane, 1u), &stg[kIndBlock]);
-        }
+        for (uint32_t j = 0; j < kIndBlock / 128; ++j) glds16(E + min(vb + 128 * j + 2 * lane, qmax), &stg[128 * j]);
     };
     auto stage = [&](uint32_t vb) {  // into the ring: entries known when loaded
-        const int d = qwin(vb) & 1;
         vm_drain();
         uint2 x[kIndSlices];
 #pragma unroll
-        for (uint32_t k = 0; k < kIndSlices; ++k) x[k] = stg[wof(64 * k + lane, d)];
+        for (uint32_t k = 0; k < kIndSlices; ++k) x[k] = stg[64 * k + lane];
         asm volatile("" ::: "memory");  // every read issued before the first write
 #pragma unroll
         for (uint32_t k = 0; k < kIndSlices; ++k) {
             const uint32_t v = vb + 64 * k + lane;
-            if (v < n && x[k].x != kIndPend) ring[v % kIndRing] = x[k];
+            if (v < nc && x[k].x != kIndPend) ring[v % kIndRing] = x[k];
         }
     };
-    auto flush = [&](uint32_t vb) {  // the block's symbols to ll, 16 bytes per lane
-        const int qw = qwin(vb), qf = qw & ~15;
-        const int lo = max(qw, 0), hi = min(qw + (int)kIndBlock, (int)n);  // the block's positions
-        const uint32_t w = 16 * lane;
-        if (w < kIndBlock + 32 && (int)w < hi - qf) {
-            uint4 f = *(const uint4*)&fin[w];  // the bytes before each rotation, mapped to symbols here
-            if (!u2s_id) {
-                uint32_t* fw = &f.x;
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const uint32_t x = fw[r];
-                    fw[r] = (uint32_t)u2s[x & 255u] | ((uint32_t)u2s[(x >> 8) & 255u] << 8) |
-                            ((uint32_t)u2s[(x >> 16) & 255u] << 16) | ((uint32_t)u2s[x >> 24] << 24);
-                }
-            }
-            const int q = qf + (int)w;
-            if (q >= lo && q + 15 < hi) {
-                *(uint4*)(LL + q) = f;
-            } else {
-                const uint32_t fv[4] = {f.x, f.y, f.z, f.w};
-#pragma unroll
-                for (int r = 0; r < 16; ++r)
-                    if (q + r >= lo && q + r < hi) LL[q + r] = (uint8_t)(fv[r >> 2] >> (8 * (r & 3)));
-            }
-        }
-    };
-    __syncthreads();
     issue(0);
     stage(0);
     bool bad = false;  // inconsistent counts or a pending entry no earlier lane places (never)
     uint32_t org = ~0u;
-    for (uint32_t v0 = 0; v0 < n && !bad; v0 += kIndBlock) {
+    for (uint32_t v0 = 0; v0 < nc && !bad; v0 += kIndBlock) {
         // the next block's ring slots held the previous block: not placed yet
 #pragma unroll
         for (uint32_t k = 0; k < kIndSlices; ++k) ring[(v0 + kIndBlock + 64 * k + lane) % kIndRing].x = kIndPend;
-        const bool more = v0 + kIndBlock < n;
+        const bool more = v0 + kIndBlock < nc;
         if (more) issue(v0 + kIndBlock);
-        // steps of kIndStepSlices slices: item k of lane l is position
+        // steps of kIndStepSlices slices: item k of lane l is compact index
         // vs + 64 k + l, and the scan order is (k, l)
-        for (uint32_t vs = v0; vs < min(n, v0 + kIndBlock) && !bad; vs += 64 * kIndStepSlices) {
+        for (uint32_t vs = v0; vs < min(nc, v0 + kIndBlock) && !bad; vs += 64 * kIndStepSlices) {
             constexpr int KS = kIndStepSlices;
             uint2 e[KS];
             uint64_t todo[KS];
 #pragma unroll
             for (int k = 0; k < KS; ++k) {
                 const uint32_t v = vs + 64 * k + lane;
-                todo[k] = __ballot(v < n);
+                todo[k] = __ballot(v < nc);
                 e[k] = ring[v % kIndRing];
             }
             // rounds up to the first pending entry: one round unless an entry
@@ -2009,68 +2021,22 @@ __global__ __launch_bounds__(64) void bwt_induce(Batch B)
                     b[k] = (lo >> 24) ^ mir;
                     const uint32_t u = (hi >> 24) ^ mir;
                     ind[k] = me && (b[k] > u || (b[k] == u && (lo & kIndPlaced)));
-                    if (me) fin[wof(vs - v0 + 64 * k + lane, qwin(v0) & 15)] = (uint8_t)(lo >> 24);
-                    org = me && (lo & kIndIdx) == 0 ? qof(vs + 64 * k + lane) : org;  // origPtr: rotation 0
                     rem[k] = __ballot(ind[k]);
                     left |= rem[k];
                 }
                 if (left) {
-                    // ranks among the inducing entries with the same b, in
-                    // scan order: a round of ballots per distinct b
-                    uint32_t rank[KS], tot_of[KS];
-                    bool inm[KS];
-#pragma unroll
-                    for (int k = 0; k < KS; ++k) {
-                        rank[k] = 0;
-                        tot_of[k] = 0;
-                    }
-                    while (left) {
-                        uint32_t bl = 0;
-                        bool got = false;
-#pragma unroll
-                        for (int k = 0; k < KS; ++k)
-                            if (!got && rem[k]) {
-                                bl = (uint32_t)__builtin_amdgcn_readlane((int)b[k], __builtin_ctzll(rem[k]));
-                                got = true;
-                            }
-                        uint32_t sb = 0;
-                        left = 0;
-#pragma unroll
-                        for (int k = 0; k < KS; ++k) {
-                            const uint64_t m = __ballot(b[k] == bl) & rem[k];
-                            inm[k] = (m >> lane) & 1u;
-                            const uint32_t r =
-                                sb + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-                            rank[k] = inm[k] ? r : rank[k];
-                            sb += (uint32_t)__popcll(m);
-                            rem[k] &= ~m;
-                            left |= rem[k];
-                        }
-#pragma unroll
-                        for (int k = 0; k < KS; ++k) tot_of[k] = inm[k] ? sb : tot_of[k];
-                    }
-                    uint32_t dest[KS];
-#pragma unroll
-                    for (int k = 0; k < KS; ++k) dest[k] = head[b[k]] + rank[k];  // all reads first
-#pragma unroll
-                    for (int k = 0; k < KS; ++k)
-                        if (ind[k] && rank[k] == 0) head[b[k]] = dest[k] + tot_of[k];
-                    bool over = false, np0 = false;
+                    // the induced rotation p = i - 1: its entry (T[p-1] =
+                    // T[i-2] ... and T[p] = T[i-1]), and whether it is live
+                    bool np0 = false;
                     uint32_t plo[KS], phi[KS];
 #pragma unroll
                     for (int k = 0; k < KS; ++k) {
-                        over = over || (ind[k] && dest[k] >= n);
-                        // entry of i - 1: T[p-1] = T[i-2] ... and T[p] = T[i-1]
                         const uint32_t lo = e[k].x, hi = e[k].y;
                         const uint32_t idx = lo & kIndIdx, np = (lo >> 20) & 7u;
                         const uint32_t p = idx ? idx - 1 : n - 1;
                         plo[k] = p | ((np - 1) << 20) | kIndPlaced | ((hi & 0xFFu) << 24);
                         phi[k] = ((hi >> 8) & 0xFFFFu) | (lo & 0xFF000000u);
                         np0 = np0 || (ind[k] && np == 0);
-                    }
-                    if (__any(over)) {
-                        bad = true;
-                        break;
                     }
                     if (__any(np0)) {
 #pragma unroll
@@ -2084,11 +2050,91 @@ __global__ __launch_bounds__(64) void bwt_induce(Batch B)
                             phi[k] = ((x >> 8) & 0xFFFFFFu) | (lo & 0xFF000000u);
                         }
                     }
+                    bool live[KS];
+                    uint64_t lmask[KS];
 #pragma unroll
                     for (int k = 0; k < KS; ++k) {
-                        const bool near = dest[k] < v0 + kIndRing;
-                        if (ind[k] && near) ring[dest[k] % kIndRing] = make_uint2(plo[k], phi[k]);
-                        if (ind[k] && !near) E[qof(dest[k])] = make_uint2(plo[k], phi[k]);
+                        live[k] = ind[k] && ((plo[k] >> 24) ^ mir) >= b[k];
+                        lmask[k] = __ballot(live[k]);
+                    }
+                    // ranks among the inducing entries with the same b, in
+                    // scan order, and among the live ones of them: a round of
+                    // ballots per distinct b
+                    uint32_t rank[KS], tot_of[KS], lrank[KS], ltot_of[KS];
+                    bool inm[KS];
+#pragma unroll
+                    for (int k = 0; k < KS; ++k) {
+                        rank[k] = 0;
+                        tot_of[k] = 0;
+                        lrank[k] = 0;
+                        ltot_of[k] = 0;
+                    }
+                    while (left) {
+                        uint32_t bl = 0;
+                        bool got = false;
+#pragma unroll
+                        for (int k = 0; k < KS; ++k)
+                            if (!got && rem[k]) {
+                                bl = (uint32_t)__builtin_amdgcn_readlane((int)b[k], __builtin_ctzll(rem[k]));
+                                got = true;
+                            }
+                        uint32_t sb = 0, sl = 0;
+                        left = 0;
+#pragma unroll
+                        for (int k = 0; k < KS; ++k) {
+                            const uint64_t m = __ballot(b[k] == bl) & rem[k], ml = m & lmask[k];
+                            inm[k] = (m >> lane) & 1u;
+                            const uint32_t r =
+                                sb + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+                            const uint32_t rl =
+                                sl + __builtin_amdgcn_mbcnt_hi((uint32_t)(ml >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)ml, 0u));
+                            rank[k] = inm[k] ? r : rank[k];
+                            lrank[k] = inm[k] ? rl : lrank[k];
+                            sb += (uint32_t)__popcll(m);
+                            sl += (uint32_t)__popcll(ml);
+                            rem[k] &= ~m;
+                            left |= rem[k];
+                        }
+#pragma unroll
+                        for (int k = 0; k < KS; ++k) {
+                            tot_of[k] = inm[k] ? sb : tot_of[k];
+                            ltot_of[k] = inm[k] ? sl : ltot_of[k];
+                        }
+                    }
+                    // final scan position, and compact index if live (the
+                    // first lane of each b has lrank 0 and moves both counters)
+                    uint32_t dest[KS], cdest[KS], dlim[KS], cdlim[KS];
+#pragma unroll
+                    for (int k = 0; k < KS; ++k) {  // all reads first
+                        dest[k] = head[b[k]] + rank[k];
+                        cdest[k] = chead[b[k]] + lrank[k];
+                        dlim[k] = hlim[b[k]];
+                        cdlim[k] = clim[b[k]];
+                    }
+#pragma unroll
+                    for (int k = 0; k < KS; ++k)
+                        if (ind[k] && rank[k] == 0) {
+                            head[b[k]] = dest[k] + tot_of[k];
+                            chead[b[k]] = cdest[k] + ltot_of[k];
+                        }
+                    bool over = false;
+#pragma unroll
+                    for (int k = 0; k < KS; ++k)
+                        over = over || (ind[k] && dest[k] >= dlim[k]) || (live[k] && cdest[k] >= cdlim[k]);
+                    if (__any(over)) {  // past the bucket's part: the counts do not fit the scan
+                        bad = true;
+                        break;
+                    }
+#pragma unroll
+                    for (int k = 0; k < KS; ++k) {
+                        if (ind[k]) {  // the symbol at the final position; origPtr at rotation 0
+                            const uint32_t q = qof(dest[k]), y = plo[k] >> 24;
+                            LL[q] = u2s_id ? (uint8_t)y : u2s[y];
+                            if ((plo[k] & kIndIdx) == 0) org = q;
+                        }
+                        const bool near = cdest[k] < v0 + kIndRing;
+                        if (live[k] && near) ring[cdest[k] % kIndRing] = make_uint2(plo[k], phi[k]);
+                        if (live[k] && !near) E[cdest[k]] = make_uint2(plo[k], phi[k]);
                     }
                 }
                 if (!anyp) break;
@@ -2103,9 +2149,15 @@ __global__ __launch_bounds__(64) void bwt_induce(Batch B)
                 for (int k = 0; k < KS; ++k) e[k] = ring[(vs + 64 * k + lane) % kIndRing];
             }
         }
-        if (!bad) flush(v0);
         if (more && !bad) stage(v0 + kIndBlock);
     }
+    // every placed rotation induced once, every live slot filled
+    __syncthreads();
+    bool short_of = false;
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+        short_of = short_of || head[4 * lane + q] != hlim[4 * lane + q] || chead[4 * lane + q] != clim[4 * lane + q];
+    bad = bad || __any(short_of);
     if (bad && lane == 0) B.flags[s] |= kFlagHost;  // the host library redoes the stream
     if (org != ~0u) B.orig_ptr[s] = org;
 }
@@ -4064,14 +4116,12 @@ int bzip2_blocks(const void* d_img, const uint32_t dims[5], const uint32_t bs[5]
     BwtStats bwt_stats;
     if (bwt_sort(B, S, st, &bwt_stats) != hipSuccess) return LFM_HIP_ERUNTIME;
     if (!B.it_full) {
-        // the other type placed by one scan; the final order in the vals_b area
-        B.sfin = B.vals_b;
+        // the other type placed by one scan, which writes the symbols ll[]
         B.ent = (uint2*)B.keys_a;
         const uint32_t chunks = (B.cap + kPlaceChunk - 1) / kPlaceChunk;
         hipLaunchKernelGGL(bwt_place_sorted, dim3(8 * chunks * ((count + 7) / 8)), dim3(256), 0, st, B, chunks);
         hipLaunchKernelGGL(bwt_induce, dim3(count), dim3(64), 0, st, B);
         if (!ok()) return LFM_HIP_ERUNTIME;
-        B.sa = B.sfin;
     }
     mark(2);
     if (t_hook) t_hook(t_hook_ctx, 1);  // the tie rounds of bwt_sort end with a host synchronisation
