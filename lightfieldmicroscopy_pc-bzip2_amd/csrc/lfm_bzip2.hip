@@ -65,6 +65,7 @@
 #include <mutex>
 #include <type_traits>
 #include <vector>
+#include "lfm_bwt_types.h"  // bwt_types8, bytes_eq, group_valid
 #include "lfm_bz_caps.h"  // rle_cap, out_cap, sel_cap, kGSize, align_up, max_parts
 #include "lfm_hip.h"
 
@@ -784,8 +785,7 @@ constexpr uint32_t kKeyBytes = 8;  // first-round key: the 8-byte prefix (0.02 %
 constexpr uint32_t kBucketBits = 14;               // 64 KiB histogram, two workgroups per CU (15 bits / one workgroup
                                                    // per CU measured 3 % slower end to end, 13 bits 18 % slower: more
                                                    // buckets overflow the small sorter)
-constexpr int kBucketThreads = 1024;
-constexpr uint32_t kBktTile = 4096;
+constexpr int kBucketThreads = 1024;               // each walks 8 positions of a tile (kBktG, kBktTile below)
 constexpr uint32_t kChunk = 1024;  // (512 equal, 2 048 slower end to end in round 5)
 constexpr int kCsThreads = 512, kCsItems = 4;      // chunks up to 2 048 (every multi-bucket chunk); 512 x 4 measured
                                                    // 10 % faster than 256 x 8
@@ -806,15 +806,25 @@ struct ChunkLists {
 
 // A tile of the text for the bucket pass: T[i0 - 1 .. i0 + m + 8) cyclically
 // in tile[kTOff - 1 .. kTOff + m + 8), m = min(n - i0, kBktTile) (T[i0 + k]
-// at tile[kTOff + k]: word-aligned stores).  bucket_fetch loads this
-// thread's part (4 bytes; one edge byte for threads 0..8) into registers, a
-// tile ahead of bucket_put, which stores it into LDS: the pass is a chain of
-// tiles, and waiting for each tile's loads was most of its time.  Tiles
-// alternate between two buffers, so one barrier per tile orders them.
-constexpr uint32_t kTOff = 4;
+// at tile[kTOff + k]: 8-byte aligned stores and group reads).  A lane walks a
+// group of kBktG = 8 consecutive positions from registers: bucket_fetch loads
+// this thread's part (8 bytes; one edge byte for threads 0..8) a tile ahead,
+// bucket_put stores it into LDS, bucket_group reads the lane's group, the 8
+// bytes after it and the byte before it back.  One LDS buffer: the tile is
+// double-buffered through the lanes' registers instead (two 8 KiB buffers
+// beside the 64 KiB histogram would leave one workgroup per CU), so a tile
+// costs two barriers, the second straight after the group reads -- as many per
+// byte as one barrier per 4 096-byte tile.
+constexpr uint32_t kBktG = 8;
+constexpr uint32_t kBktTile = kBucketThreads * kBktG;
+constexpr uint32_t kTOff = 8;
 struct BktPart {
-    uint32_t w;
+    uint2 w;
     uint32_t e;
+};
+struct BktGroup {
+    uint64_t P, Q;  // T[i0 + 8 t ..] big endian (lfm_bwt_types.h)
+    uint32_t prev;  // T[i0 + 8 t - 1]
 };
 
 __device__ __forceinline__ BktPart bucket_fetch(const uint8_t* __restrict__ T, uint32_t n, uint32_t i0)
@@ -824,12 +834,15 @@ __device__ __forceinline__ BktPart bucket_fetch(const uint8_t* __restrict__ T, u
     const uint32_t t = threadIdx.x;
     const uint32_t i0c = min(i0, n ? n - 1 : 0u);
     const uint32_t m = n > i0c ? min(n - i0c, kBktTile) : 0u;
-    // 4 bytes (may read up to 3 bytes past n: inside the stream's cap)
-    const uint32_t w = *(const uint32_t*)(T + min(i0c + 4 * t, n ? (n - 1) & ~3u : 0u));
+    // 8 bytes (may read up to 7 bytes past n: inside the stream's cap, which
+    // is a multiple of 256 and leaves 8 bytes after n)
+    const uint2 w = *(const uint2*)(T + min(i0c + kBktG * t, n ? (n - 1) & ~7u : 0u));
     uint32_t j = n ? (t < 8 ? (i0c + m + t) % n : (i0c ? i0c - 1 : n - 1)) : 0u;
     const uint32_t e = T[j];
+    const bool in = i0 < n && kBktG * t < m;
     BktPart p;
-    p.w = (i0 < n && 4 * t < m) ? w : 0u;
+    p.w.x = in ? w.x : 0u;
+    p.w.y = in ? w.y : 0u;
     p.e = (i0 < n && t <= 8) ? e : 0u;
     return p;
 }
@@ -838,14 +851,49 @@ __device__ __forceinline__ uint32_t bucket_put(const BktPart& p, uint32_t n, uin
 {
     const uint32_t t = threadIdx.x;
     const uint32_t m = min(n - i0, kBktTile);
-    if (4 * t + 4 <= m) {
-        *(uint32_t*)(tile + kTOff + 4 * t) = p.w;
-    } else if (4 * t < m) {  // the last partial word: its valid bytes only (the edge bytes follow)
-        for (uint32_t b = 0; b < m - 4 * t; ++b) tile[kTOff + 4 * t + b] = (uint8_t)(p.w >> (8 * b));
+    if (kBktG * t + kBktG <= m) {
+        *(uint2*)(tile + kTOff + kBktG * t) = p.w;
+    } else if (kBktG * t < m) {  // the last partial group: its valid bytes only (the edge bytes follow)
+        const uint64_t w = (uint64_t)p.w.x | ((uint64_t)p.w.y << 32);
+        for (uint32_t b = 0; b < m - kBktG * t; ++b) tile[kTOff + kBktG * t + b] = (uint8_t)(w >> (8 * b));
     }
     if (t < 8) tile[kTOff + m + t] = (uint8_t)p.e;
     else if (t == 8) tile[kTOff - 1] = (uint8_t)p.e;
     return m;  // the caller's barrier publishes the tile
+}
+
+// this lane's group (the bytes past T[i0 + m + 8) are whatever the buffer
+// held: no valid position's type or key reads them)
+__device__ __forceinline__ BktGroup bucket_group(const uint8_t* tile)
+{
+    const uint8_t* p = tile + kTOff + kBktG * threadIdx.x;
+    BktGroup g;
+    g.P = __builtin_bswap64(*(const uint64_t*)p);
+    g.Q = __builtin_bswap64(*(const uint64_t*)(p + 8));
+    g.prev = p[-1];
+    return g;
+}
+
+// position j of a group: its bucket (the top BITS bits of T[j], T[j + 1]),
+// its first byte and the byte before it
+template <uint32_t BITS>
+__device__ __forceinline__ uint32_t group_key(const BktGroup& g, uint32_t j)
+{
+    const uint32_t ab = j < 7u ? (uint32_t)(g.P >> (48u - 8u * j)) & 0xFFFFu
+                               : (((uint32_t)g.P & 0xFFu) << 8) | (uint32_t)(g.Q >> 56);
+    return ab >> (16 - BITS);
+}
+__device__ __forceinline__ uint32_t group_byte(const BktGroup& g, uint32_t j)
+{
+    return (uint32_t)(g.P >> (56u - 8u * j)) & 0xFFu;
+}
+__device__ __forceinline__ uint32_t group_prev(const BktGroup& g, uint32_t j)
+{
+    return j ? group_byte(g, j - 1u) : g.prev;
+}
+__device__ __forceinline__ bool group_has(uint64_t flags, uint32_t j)
+{
+    return (flags >> (63u - 8u * j)) & 1u;
 }
 
 // LDS slot of bucket `key` (BITS bits: the first byte, then the top BITS - 8
@@ -874,27 +922,33 @@ __device__ __forceinline__ uint32_t bkt_slot(uint32_t key)
 // the B ones (kModeSortA).  The pass sorts the A rotations unless the B ones
 // are clearly fewer: on 16-bit little-endian symbols the A rotations start at
 // the low bytes, whose first byte spreads them over the buckets, while the B
-// ones start at the (mostly zero) high bytes.  rot_type reads tile[kTOff + k + d]
-// for d <= 8 (the tile holds 8 bytes past its end): 1 = B, 0 = A, 2 = still
-// undecided after 8 equal bytes (only runs of 0xFB survive RLE1 that long: the
-// stream is then sorted whole, kModeFull).
+// ones start at the (mostly zero) high bytes.  bwt_types8 (lfm_bwt_types.h)
+// decides the types of a lane's 8 positions from their bytes and the 8 after
+// them (the tile holds 8 bytes past its end), by byte-wise comparisons on
+// words; a type still undecided after 8 equal bytes (only runs of 0xFB
+// survive RLE1 that long) sends the stream through the sort whole, kModeFull.
 constexpr uint32_t kModeSortA = 0, kModeSortB = 1, kModeFull = 2;
 
-__device__ __forceinline__ uint32_t rot_type(const uint8_t* tile, uint32_t k, uint32_t a, uint32_t b)
+// The rotations of a lane's group that go through the sort in `mode`, as
+// flags (lfm_bwt_types.h); m: the tile's length.  A group past m has none.
+struct BktSorted {
+    uint64_t valid, sorted;
+    BwtTypes ty;  // (not in kModeFull)
+};
+__device__ __forceinline__ BktSorted group_sorted(const BktGroup& g, uint32_t m, uint32_t mode)
 {
-    if (a != b) return a < b ? 1u : 0u;
-#pragma unroll 1
-    for (uint32_t d = 1; d < 8; ++d) {
-        const uint32_t x = tile[kTOff + k + d], y = tile[kTOff + 1 + k + d];
-        if (x != y) return x < y ? 1u : 0u;
+    const uint32_t k = kBktG * threadIdx.x;
+    BktSorted r;
+    r.valid = k < m ? group_valid(min(m - k, kBktG)) : 0ull;
+    r.ty = BwtTypes{0, 0, 0, 0};
+    if (mode == kModeFull) {
+        r.sorted = r.valid;
+    } else {
+        r.ty = bwt_types8(g.P, g.Q, k < m ? min(m - k, kBktG) : 1u);
+        r.sorted = (mode == kModeSortB ? r.ty.b : ~r.ty.b) & r.valid;
+        if (k >= m) r.ty.undecided = 0;
     }
-    return 2u;
-}
-
-// does rotation k of the tile (first bytes a, b) go through the sort in `mode`
-__device__ __forceinline__ bool rot_sorted(const uint8_t* tile, uint32_t k, uint32_t a, uint32_t b, uint32_t mode)
-{
-    return mode == kModeFull || rot_type(tile, k, a, b) == (mode == kModeSortB ? 1u : 0u);
+    return r;
 }
 
 template <uint32_t BITS>
@@ -902,7 +956,7 @@ __global__ __launch_bounds__(kBucketThreads) __attribute__((amdgpu_waves_per_eu(
 {
     constexpr uint32_t kBuckets = 1u << BITS;
     __shared__ uint32_t hist[kBuckets];  // 64 KiB at 14 bits
-    __shared__ __attribute__((aligned(16))) uint8_t tiles[2][kBktTile + 16];
+    __shared__ __attribute__((aligned(16))) uint8_t tile[kTOff + kBktTile + 8];  // (a last group's 16 bytes end here)
     __shared__ uint32_t cuts[kMaxCuts];
     __shared__ uint32_t wsum[kBucketThreads / 64], wcut[kBucketThreads / 64];
     __shared__ uint32_t ccount[4], cbase[4];
@@ -929,56 +983,47 @@ __global__ __launch_bounds__(kBucketThreads) __attribute__((amdgpu_waves_per_eu(
         __syncthreads();
         // unsorted rotations starting with byte 0 (the high bytes of small
         // 16-bit symbols: about half of all rotations) are counted in a
-        // register -- their LDS atomics all hit one word and serialise
+        // register, by popcounts of the group's masks -- their LDS atomics
+        // all hit one word and serialise
         uint32_t u_zero = 0, l_zero = 0;
-        // sorted rotations in buckets a << (BITS - 8) for a < 4 (a small low
-        // byte, then a zero high byte: the hottest buckets) likewise, in
-        // 16-bit register fields
-        uint32_t hot01 = 0, hot23 = 0;
+        mode = __builtin_amdgcn_readfirstlane(mode);  // (the same in every lane: kept on the scalar side)
         BktPart nx = bucket_fetch(T, n, 0);
-        for (uint32_t i0 = 0, it = 0; i0 < n; i0 += kBktTile, ++it) {
+        for (uint32_t i0 = 0; i0 < n; i0 += kBktTile) {
             const BktPart cur = nx;
             nx = bucket_fetch(T, n, i0 + kBktTile);
-            uint8_t* tile = tiles[it & 1];
             const uint32_t m = bucket_put(cur, n, i0, tile);
             __syncthreads();
-            for (uint32_t k = t; k < m; k += kBucketThreads) {
-                const uint32_t a = tile[kTOff + k], b = tile[kTOff + 1 + k];
-                const uint32_t ty = mode == kModeFull ? 3u : rot_type(tile, k, a, b);
-                if (ty == 2u) undecided = 1u;
-                else if (mode == kModeFull || ty == (mode == kModeSortB ? 1u : 0u)) {
-                    const uint32_t key = (a << (BITS - 8)) | (b >> (16 - BITS));
-                    if (key < (4u << (BITS - 8)) && (key & ((1u << (BITS - 8)) - 1u)) == 0u) {
-                        const uint32_t inc = 1u << (16u * (a & 1u));
-                        if (a < 2u) hot01 += inc;
-                        else hot23 += inc;
-                    } else {
-                        atomicAdd(&hist[bkt_slot<BITS>(key)], 1u);
-                    }
-                }
-                else {
-                    // an unsorted rotation k induces k - 1 ("live") when k - 1
-                    // is unsorted too: by bwt_induce's own byte rule, T[k-1]
-                    // against T[k] in the direction of the mode's scan
-                    const uint32_t pb = tile[kTOff + k - 1];
-                    const bool live = mode == kModeSortA ? pb <= a : pb >= a;
-                    if (a == 0u) {
-                        ++u_zero;
-                        l_zero += live;
-                    } else {
-                        atomicAdd(&cnt_u[a], 1u);
-                        if (live) atomicAdd(&cnt_l[a], 1u);
-                    }
-                }
+            const BktGroup g = bucket_group(tile);
+            __syncthreads();
+            const BktSorted r = group_sorted(g, m, mode);
+            if (r.ty.undecided) undecided = 1u;
+            // an unsorted rotation k induces k - 1 ("live") when k - 1 is
+            // unsorted too: by bwt_induce's own byte rule, T[k-1] against T[k]
+            // in the direction of the mode's scan.  For the group's later
+            // positions that is the comparison of the position before.
+            const uint64_t unsorted = r.valid & ~r.sorted;
+            const uint32_t first = (uint32_t)(g.P >> 56);
+            const uint64_t step = mode == kModeSortA ? r.ty.lt | r.ty.eq : ~r.ty.lt & kByteFlags;
+            const uint64_t live = (step >> 8) | ((mode == kModeSortA ? g.prev <= first : g.prev >= first) ? 1ull << 63 : 0ull);
+            const uint64_t uz = unsorted & bytes_eq(g.P, 0);
+            u_zero += __popcll(uz);
+            l_zero += __popcll(uz & live);
+            // one atomic per counted position, its word chosen without a
+            // branch: the bucket of a sorted rotation, else the first byte
+            const uint64_t rest = unsorted & ~uz, counted = r.sorted | rest;
+#pragma unroll
+            for (uint32_t j = 0; j < kBktG; ++j) {
+                uint32_t* word = group_has(r.sorted, j) ? &hist[bkt_slot<BITS>(group_key<BITS>(g, j))] : &cnt_u[group_byte(g, j)];
+                if (group_has(counted, j)) atomicAdd(word, 1u);
+            }
+            if (rest & live) {  // (few on 16-bit symbols: their unsorted rotations start with the zero high bytes)
+#pragma unroll
+                for (uint32_t j = 0; j < kBktG; ++j)
+                    if (group_has(rest & live, j)) atomicAdd(&cnt_l[group_byte(g, j)], 1u);
             }
         }
         if (u_zero) atomicAdd(&cnt_u[0], u_zero);
         if (l_zero) atomicAdd(&cnt_l[0], l_zero);
-#pragma unroll
-        for (uint32_t h = 0; h < 4; ++h) {
-            const uint32_t c = ((h < 2u ? hot01 : hot23) >> (16u * (h & 1u))) & 0xFFFFu;
-            if (c) atomicAdd(&hist[bkt_slot<BITS>(h << (BITS - 8))], c);
-        }
         __syncthreads();
         if (mode == kModeFull) break;
         if (undecided) {
@@ -1141,18 +1186,19 @@ __global__ __launch_bounds__(kBucketThreads) __attribute__((amdgpu_waves_per_eu(
     // rebuild the 8-byte keys from the text (rot_key8_fast), which the L2s
     // hold, instead of 8-byte scattered key writes and their re-read
     BktPart nx = bucket_fetch(T, n, 0);
-    for (uint32_t i0 = 0, it = 0; i0 < n; i0 += kBktTile, ++it) {
+    for (uint32_t i0 = 0; i0 < n; i0 += kBktTile) {
         const BktPart cur = nx;
         nx = bucket_fetch(T, n, i0 + kBktTile);
-        uint8_t* tile = tiles[it & 1];
         const uint32_t m = bucket_put(cur, n, i0, tile);
         __syncthreads();
-        for (uint32_t k = t; k < m; k += kBucketThreads) {
-            const uint8_t* p = tile + kTOff + k;
-            const uint32_t a = p[0], b = p[1];
-            if (rot_sorted(tile, k, a, b, mode)) {
-                const uint32_t pos = atomicAdd(&hist[bkt_slot<BITS>((a << (BITS - 8)) | (b >> (16 - BITS)))], 1u);
-                B.vals_a[o + pos] = (i0 + k) | ((uint32_t)p[-1] << 24);
+        const BktGroup g = bucket_group(tile);
+        __syncthreads();
+        const uint64_t sorted = group_sorted(g, m, mode).sorted;
+#pragma unroll
+        for (uint32_t j = 0; j < kBktG; ++j) {
+            if (group_has(sorted, j)) {
+                const uint32_t pos = atomicAdd(&hist[bkt_slot<BITS>(group_key<BITS>(g, j))], 1u);
+                B.vals_a[o + pos] = (i0 + kBktG * t + j) | (group_prev(g, j) << 24);
             }
         }
     }
