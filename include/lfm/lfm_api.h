@@ -182,14 +182,28 @@ LFM_API int lfm_get_bzip2_multiblock(void);
  * LFM_BUNZIP2_MULTIBLOCK=0 starts with 0): streams of several bzip2 blocks are
  * decoded on the GPU like single-block ones, in every reader that decodes on
  * the GPU (whole images and regions, host and device destinations, one device
- * or several); only streams with a periodic block (and malformed ones) still
- * go to the host library.  0: every such stream is decoded by the host
+ * or several); only streams with a periodic block (see
+ * lfm_set_bunzip2_periodic) and malformed ones still go to the host library.
+ * 0: every such stream is decoded by the host
  * library, one after the other, as before this switch existed.  The pixels
  * are the same either way; lfm_decode_stats.host_blocks tells the two apart.
  * The setter returns the previous value; it applies to decodes started after
  * it. */
 LFM_API int lfm_set_bunzip2_multiblock(int on);
 LFM_API int lfm_get_bunzip2_multiblock(void);
+/* GPU decode of bzip2 blocks whose text after bzip2's first run-length stage
+ * is exactly periodic (w w ... w): in an unpredicted file any 16-bit region of
+ * one value whose two bytes differ, a camera offset of 100 for one.  0 (the
+ * default; env LFM_BUNZIP2_PERIODIC=1 starts with 1): streams with such a
+ * block are decoded by the host library, one after the other, as before this
+ * switch existed.  1: they are decoded on the GPU like any other stream, in
+ * every reader that decodes on the GPU (whole images and regions, host and
+ * device destinations, one device or several).  The pixels are the same
+ * either way; lfm_decode_stats.host_blocks tells the two apart.  The setter
+ * returns the previous value; it applies to decodes started after it.
+ * (lfm_hip_bunzip2_set_periodic, lfm_hip.h, is the same switch.) */
+LFM_API int lfm_set_bunzip2_periodic(int on);
+LFM_API int lfm_get_bunzip2_periodic(void);
 /* How the bzip2 streams (one per 5-D block) of the last encode were compressed
  * that lfm_encoder_encode, lfm_encoder_encode_slab or lfm_encoder_wait
  * completed on this encoder: all streams, those the host library compressed,

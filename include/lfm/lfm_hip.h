@@ -142,7 +142,8 @@ void lfm_hip_bzip2_set_stage_hook(void (*fn)(void* ctx, int stage), void* ctx);
  * (host array of count + 1 byte offsets) and decodes into d_out + i *
  * out_stride.  h_lens[i] = decoded bytes; h_flags[i]: 0 ok, 1 decode this
  * stream with the host library (several blocks, randomised, malformed,
- * larger than out_stride), 2 block CRC mismatch.  d_ws:
+ * larger than out_stride, or periodic: lfm_hip_bunzip2_set_periodic below),
+ * 2 block CRC mismatch.  d_ws:
  * lfm_hip_bunzip2_workspace_bytes(count, out_stride).  Synchronous. */
 size_t lfm_hip_bunzip2_workspace_bytes(uint32_t count, uint32_t out_stride);
 int lfm_hip_bunzip2_blocks(const void* d_payload, const uint64_t* h_offs, uint32_t count, void* d_out,
@@ -168,8 +169,8 @@ int lfm_hip_bunzip2_issue(const void* d_payload, const uint64_t* h_offs, uint32_
  * it, each checked against its own CRC and the stream's combined CRC against
  * their fold.  h_lens[i] is the stream's decoded length and h_flags[i] as
  * above: 1 for a stream with more blocks than slots, a block above the
- * level's size, a periodic block, a damaged magic or combined CRC or more
- * than out_stride decoded bytes (nothing of a part that does not fit is
+ * level's size, a periodic block (unless lfm_hip_bunzip2_set_periodic(1), see
+ * below), a damaged magic or combined CRC or more than out_stride decoded bytes (nothing of a part that does not fit is
  * written); 2 when a block's bytes do not match its CRC.  Where max_parts is 1
  * (the default 96x96x8 uint16 block at its level 2) the size, the layout and
  * the launches are those of the single-block pair.  The workspace is
@@ -183,6 +184,20 @@ int lfm_hip_bunzip2_blocks_multi(const void* d_payload, const uint64_t* h_offs, 
 int lfm_hip_bunzip2_issue_multi(const void* d_payload, const uint64_t* h_offs, uint32_t count, void* d_out,
                                 uint32_t out_stride, uint32_t level, void* d_ws, size_t ws_bytes, uint32_t* h_lens,
                                 uint32_t* h_flags, void* stream);
+/* bzip2 blocks whose text after RLE1 is exactly periodic (w w ... w: a constant
+ * 16-bit value with two different bytes, for one).  Their LF permutation has
+ * several cycles, and libbzip2's n steps from origPtr go n / q times round
+ * the one of the start, of the period's length q.  One process-wide switch
+ * for the four entries above, read once per call, when the call is issued.
+ * 0 (the default; env LFM_BUNZIP2_PERIODIC=1 starts with 1): such a block's
+ * stream comes back with flag 1, as before this switch existed.  1: the
+ * inverse BWT places the q bytes of one trip and repeats them up to n, the
+ * same bytes libbzip2 gives, whatever q and n are; the block's CRC decides
+ * as for any other block (flag 2 for an origPtr that names a row of another
+ * cycle).  The setter returns the previous value.  Neither makes a device
+ * call. */
+int lfm_hip_bunzip2_set_periodic(int on);
+int lfm_hip_bunzip2_get_periodic(void);
 
 /* Decoded blocks first .. first + count - 1 (block i at d_blocks + (i -
  * first) * stride, x fastest) back into the device image (the inverse of the

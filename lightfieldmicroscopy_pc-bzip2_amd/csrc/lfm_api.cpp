@@ -189,6 +189,8 @@ extern "C" int lfm_set_bzip2_multiblock(int on) { return lfm::set_bzip2_multiblo
 extern "C" int lfm_get_bzip2_multiblock(void) { return lfm::bzip2_multiblock(); }
 extern "C" int lfm_set_bunzip2_multiblock(int on) { return lfm::set_bunzip2_multiblock(on); }
 extern "C" int lfm_get_bunzip2_multiblock(void) { return lfm::bunzip2_multiblock(); }
+extern "C" int lfm_set_bunzip2_periodic(int on) { return lfm_hip_bunzip2_set_periodic(on); }
+extern "C" int lfm_get_bunzip2_periodic(void) { return lfm_hip_bunzip2_get_periodic(); }
 
 extern "C" int lfm_encoder_stream_counts(lfm_encoder* e, uint64_t* streams, uint64_t* host_streams,
                                          uint64_t* bzip2_blocks)

@@ -23,6 +23,13 @@
 //               segments to their output offsets, the kept bytes are copied into
 //               place (a wave per segment) and only the rare longer segments
 //               are walked again from where their walker stopped keeping.
+//               A block whose text is exactly periodic (w w ... w) has an LF
+//               permutation of several cycles; libbzip2's n steps from origPtr
+//               go round the start's cycle, of the period's length q, n / q
+//               times.  With lfm_hip_bunzip2_set_periodic(1) the chain places
+//               the q bytes of that one trip and the block's threads repeat
+//               them up to n; with 0 (the default) such a block is flagged for
+//               the host, as before the switch existed.
 //   bzd_rle1    one wave per stream: RLE1 decode (4 equal bytes + a count) into
 //               the output block from 64 text segments (their start states
 //               resolved by running every start state), CRC-32 of the block in
@@ -44,6 +51,7 @@
 // same layout and the same kernels.
 #include <hip/hip_runtime.h>
 #include <algorithm>
+#include <atomic>
 #include <cstdint>
 #include <cstdlib>
 #include <cstring>
@@ -53,6 +61,9 @@
 
 #ifndef LFM_BZD_PROBE
 #define LFM_BZD_PROBE 0  // timing probes of bzd_huff (scripts only; 0 in the library)
+#endif
+#ifndef LFM_BZD_FILL_BYTES
+#define LFM_BZD_FILL_BYTES 0  // bzd_walk's periodic fill with byte stores only (scripts only; 0 in the library)
 #endif
 
 namespace lfm {
@@ -100,6 +111,9 @@ struct Dec {
     uint32_t parts;
     uint32_t* s_len;          // per stream: decoded bytes
     uint32_t* s_flag;         // per stream: 0, kHost or kCrcFail
+    // a block whose LF permutation has several cycles (a periodic text) is
+    // decoded as libbzip2 decodes it, n steps from origPtr; 0: it is flagged kHost
+    uint32_t periodic;
 };
 
 // MSB-first bit reader over the payload: a 64-bit window of two big-endian
@@ -839,7 +853,7 @@ template <int NT, bool LDSM, bool MULTI>
 __global__ __launch_bounds__(NT) void bzd_walk(Dec D)
 {
     extern __shared__ uint32_t wsm[];  // LDSM: 4 x mcap words
-    __shared__ uint32_t s_total;
+    __shared__ uint32_t s_total;  // bytes the chain placed: n, q < n (periodic, D.periodic) or 0 (kHost)
     const uint32_t s = blockIdx.x, t = threadIdx.x;
     if (D.flags[s]) return;
     const uint32_t n = D.n[s];
@@ -879,6 +893,7 @@ __global__ __launch_bounds__(NT) void bzd_walk(Dec D)
         mnext[id] = nx;
         mlen[id] = len;
         mres[id] = res;
+        if (D.periodic) mstart[id] = ~0u;  // not on the start's cycle, until the chain says so
     }
     __syncthreads();
     // chain the segments from the start (one lane).  The markers of the
@@ -887,7 +902,10 @@ __global__ __launch_bounds__(NT) void bzd_walk(Dec D)
     // every segment has had its turn there are several cycles (a periodic
     // text), and further trips must not count (w w with two walkers, one per
     // cycle, would reach off == n and k == nwalk on the second trip, leaving
-    // the other segment's mstart unwritten)
+    // the other segment's mstart unwritten).  The trip's length q is then the
+    // period: libbzip2's n steps from origPtr go round that one cycle n / q
+    // times, so with D.periodic the q bytes of the trip are placed and
+    // repeated below; the segments of the other cycles keep mstart == ~0u
     if (t == 0) {
         const uint32_t id0 = extra ? nm : v0 / kMark;
         uint32_t id = id0, off = 0, k = 0;
@@ -898,24 +916,28 @@ __global__ __launch_bounds__(NT) void bzd_walk(Dec D)
             ++k;
             if (id == id0) break;
         }
-        s_total = off == n && k == nwalk ? 1u : 0u;
+        if (off == n) s_total = k == nwalk ? n : 0u;
+        else s_total = D.periodic && id == id0 && off < n ? off : 0u;
     }
     __syncthreads();
-    if (!s_total) {
-        if (t == 0) D.flags[s] = kHost;  // not one cycle: not a valid bzip2 block
+    const uint32_t q = s_total;
+    if (!q) {
+        if (t == 0) D.flags[s] = kHost;  // not one cycle (and D.periodic off), or not a permutation's chain
         return;
     }
+    const bool part = q < n;  // only the start's cycle has output offsets
     // pass 2: the kept bytes into place, one wave per segment
     const uint32_t lane = t & 63, wave = t >> 6;
     for (uint32_t id = wave; id < nwalk; id += NT / 64) {
         const uint32_t o = mstart[id], m = min(mlen[id], kWalkKeep);
+        if (part && o == ~0u) continue;
         const uint8_t* src = keep + (size_t)id * kWalkKeep;
         for (uint32_t k = lane; k < m; k += 64) rle[o + k] = src[k];
     }
     // segments longer than kWalkKeep: walk on from where their walker stopped keeping
     for (uint32_t id = t; id < nwalk; id += NT) {
         const uint32_t len = mlen[id];
-        if (len <= kWalkKeep) continue;
+        if (len <= kWalkKeep || (part && mstart[id] == ~0u)) continue;
         uint32_t pos = mres[id], o = mstart[id] + kWalkKeep;
         for (uint32_t k = kWalkKeep; k < len; ++k) {
             const uint32_t e = tt[pos];
@@ -923,6 +945,37 @@ __global__ __launch_bounds__(NT) void bzd_walk(Dec D)
             pos = e >> 8;
         }
     }
+    if (!part) return;
+    // the periodic text: rle[o] = rle[o mod q] for o in [q, n), reads from
+    // [0, q) only (written above, by other threads: the barrier), writes at q
+    // and up.  A thread fills one aligned 16-byte piece per step from 16 bytes
+    // of the period and stores it whole; the pieces holding q and n, which
+    // also hold bytes that are not the fill's, go byte by byte.
+    __syncthreads();
+#if LFM_BZD_FILL_BYTES
+    for (uint32_t o = q + t; o < n; o += NT) rle[o] = rle[o % q];
+#else
+    const uint32_t ab = (uint32_t)((uintptr_t)rle & 15u);  // pieces are aligned in memory
+    const uint32_t p0 = (q + ab) >> 4, p1 = (n + ab + 15u) >> 4;
+    for (uint32_t p = p0 + t; p < p1; p += NT) {
+        const uint32_t lo = max(q + ab, 16u * p) - ab, hi = min(n + ab, 16u * p + 16u) - ab;
+        uint32_t r = lo % q;
+        if (hi - lo == 16u) {
+            uint32_t w[4] = {0, 0, 0, 0};
+#pragma unroll
+            for (int j = 0; j < 16; ++j) {
+                w[j >> 2] |= (uint32_t)rle[r] << (8 * (j & 3));
+                r = r + 1u == q ? 0u : r + 1u;
+            }
+            *(uint4*)(rle + lo) = make_uint4(w[0], w[1], w[2], w[3]);
+        } else {
+            for (uint32_t o = lo; o < hi; ++o) {
+                rle[o] = rle[r];
+                r = r + 1u == q ? 0u : r + 1u;
+            }
+        }
+    }
+#endif
 }
 
 // -------------------------------------------------------------------- RLE1 --
@@ -1296,12 +1349,26 @@ uint32_t host_dcrc[256];
 uint32_t host_xpow[24];
 bool dcrc_ready = false;
 
+// periodic blocks on the device (lfm_hip_bunzip2_set_periodic; env
+// LFM_BUNZIP2_PERIODIC=1 starts with 1), read once per issue()
+std::atomic<int>& periodic_flag()
+{
+    static std::atomic<int> on{[] {
+        const char* e = std::getenv("LFM_BUNZIP2_PERIODIC");
+        return e && std::atoi(e) != 0 ? 1 : 0;
+    }()};
+    return on;
+}
+
 // level 0: the single-block entries (one slot per stream, the level from
 // out_stride); 1..9: the _multi entries
 int issue(const void* d_payload, const uint64_t* h_offs, uint32_t count, void* d_out, uint32_t out_stride,
           uint32_t level, void* d_ws, size_t ws_bytes, uint32_t* h_lens, uint32_t* h_flags, hipStream_t st);
 
 } // namespace
+
+extern "C" int lfm_hip_bunzip2_set_periodic(int on) { return periodic_flag().exchange(on ? 1 : 0); }
+extern "C" int lfm_hip_bunzip2_get_periodic(void) { return periodic_flag().load(); }
 
 extern "C" size_t lfm_hip_bunzip2_workspace_bytes(uint32_t count, uint32_t out_stride)
 {
@@ -1425,6 +1492,7 @@ int issue(const void* d_payload, const uint64_t* h_offs, uint32_t count, void* d
     D.payload = (const uint8_t*)d_payload;
     D.out_stride = out_stride;
     D.out = (uint8_t*)d_out;
+    D.periodic = periodic_flag().load() ? 1u : 0u;
     if (hipMemcpyAsync((void*)D.offs, h_offs, ((size_t)count + 1) * 8, hipMemcpyHostToDevice, st) != hipSuccess)
         return LFM_HIP_ERUNTIME;
     D.sel_cap = std::min<uint32_t>(kMaxSel, (D.cap + 49) / 50 + 64);

@@ -42,6 +42,7 @@ EXPORTS = [
     "lfm_decode_shard_plan", "lfm_decode_memory_multi", "lfm_decode_memory_multi_device",
     "lfm_set_bzip2_multiblock", "lfm_get_bzip2_multiblock", "lfm_encoder_stream_counts",
     "lfm_set_bunzip2_multiblock", "lfm_get_bunzip2_multiblock",
+    "lfm_set_bunzip2_periodic", "lfm_get_bunzip2_periodic",
     # lfm_hip.h
     "lfm_hip_predict", "lfm_hip_unpredict", "lfm_hip_unpredict_async", "lfm_hip_unpredict_check",
     "lfm_hip_unpredict_path",
@@ -51,7 +52,7 @@ EXPORTS = [
     "lfm_hip_crop_region", "lfm_hip_bzip2_workspace_bytes_multi", "lfm_hip_bzip2_max_count_multi",
     "lfm_hip_bzip2_blocks_multi", "lfm_hip_bzip2_last_blocks",
     "lfm_hip_bunzip2_max_parts", "lfm_hip_bunzip2_workspace_bytes_multi", "lfm_hip_bunzip2_blocks_multi",
-    "lfm_hip_bunzip2_issue_multi",
+    "lfm_hip_bunzip2_issue_multi", "lfm_hip_bunzip2_set_periodic", "lfm_hip_bunzip2_get_periodic",
 ]
 
 
@@ -204,6 +205,8 @@ def lib():
                                                ctypes.c_uint32, ctypes.c_uint32, vp, ctypes.c_size_t, u32p, u32p, vp]
     L.lfm_set_bunzip2_multiblock.argtypes = [ctypes.c_int]
     L.lfm_get_bunzip2_multiblock.argtypes = []
+    L.lfm_set_bunzip2_periodic.argtypes = [ctypes.c_int]
+    L.lfm_get_bunzip2_periodic.argtypes = []
     L.lfm_hip_scatter_blocks.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, u32p, u32p,
                                          ctypes.c_uint32, vp, vp]
     L.lfm_hip_select_workspace_bytes.restype = ctypes.c_size_t
@@ -980,6 +983,17 @@ def set_bunzip2_multiblock(on):
 
 def get_bunzip2_multiblock():
     return bool(lib().lfm_get_bunzip2_multiblock())
+
+
+def set_bunzip2_periodic(on):
+    """GPU decode of bzip2 blocks with an exactly periodic text on, or off (the
+    default: their streams are decoded by the host library); returns the
+    previous setting.  Applies to bunzip2_device and to every reader."""
+    return bool(lib().lfm_set_bunzip2_periodic(1 if on else 0))
+
+
+def get_bunzip2_periodic():
+    return bool(lib().lfm_get_bunzip2_periodic())
 
 
 def bunzip2_max_parts(out_stride, level):
