@@ -92,7 +92,9 @@ int lfm_hip_select(const uint16_t* d_frame, int W, int H, int T, int family, flo
  * header, bpp bytes per sample) at `level`: the compressed streams land
  * back to back in d_payload (block order); h_sizes[i] / h_flags[i] per
  * stream (flag != 0: the stream is NOT in the payload and must be produced by
- * the host library -- RLE1 block reaching nblockMAX, or a periodic block).
+ * the host library -- RLE1 block reaching nblockMAX, a periodic block, or a
+ * block above about 350 000 sorted rotations whose sort would need 1 024 chunk
+ * cuts or more).
  * d_ws: lfm_hip_bzip2_workspace_bytes(count, blockBytes); d_payload: count *
  * lfm_hip_bzip2_out_cap(blockBytes) bytes.  Synchronous. */
 size_t lfm_hip_bzip2_workspace_bytes(uint32_t count, uint32_t block_bytes);
@@ -122,6 +124,19 @@ int lfm_hip_bzip2_blocks_multi(const void* d_img, const uint32_t dims[5], const 
 /* bzip2 blocks in the payload of the calling thread's last lfm_hip_bzip2_blocks
  * or lfm_hip_bzip2_blocks_multi (one per unflagged stream for the former). */
 uint64_t lfm_hip_bzip2_last_blocks(void);
+/* The path the BWT sort of the calling thread's last lfm_hip_bzip2_blocks or
+ * lfm_hip_bzip2_blocks_multi took (read-only; counts the call had read back
+ * anyway and its host loop counters, no further synchronisation):
+ * [0..3] chunks sorted per class (at most 1 024 rotations, at most 2 048, one
+ * bucket of at most 4 096, segmented sort), [4] slots tied on their 8-byte
+ * prefix after the chunk sorts, [5] tied runs left to the tie rounds (more than
+ * 32 members, or two that agree on 72 bytes), [6] text rounds run -- [0..6] of
+ * the last attempt --, [7] 1 when the batch was sorted again with every rotation
+ * in the sort, [8] how the doubling ranks were built (0 not at all, 1 from the
+ * whole sorted order, 2 from the tied list's group keys), [9] doubling rounds
+ * run, [10] 1 when streams still tied after the last round were flagged as
+ * periodic, [11] 0. */
+void lfm_hip_bzip2_last_bwt_stats(uint32_t out[12]);
 /* Stage times (HIP events on its stream, ms) of the calling thread's last
  * lfm_hip_bzip2_blocks / lfm_hip_bzip2_blocks_multi: [0] RLE1 + CRC, [1] BWT (buckets, chunk sorts, tie
  * rounds), [2] MTF + RUNA/RUNB, [3] Huffman tables, [4] bit emission +

@@ -791,7 +791,12 @@ constexpr int kCsThreads = 512, kCsItems = 4;      // chunks up to 2 048 (every 
                                                    // 10 % faster than 256 x 8
 constexpr int kBigThreads = 512, kBigItems = 8;    // single buckets up to 4 096
 constexpr uint32_t kSmallCap = kCsThreads * kCsItems, kBigCap = kBigThreads * kBigItems;
-constexpr uint32_t kMaxCuts = 1024;                // >= 3 * cap / kChunk + 2
+constexpr uint32_t kMaxCuts = 1024;                // cut entries a stream may need, exclusive: one per kChunk sorted
+                                                   // rotations plus two per bucket above kChunk, so up to about
+                                                   // 3 * nsub / kChunk.  That stays below kMaxCuts up to ~350 000 sorted
+                                                   // rotations whatever the text (the 96 x 96 x 8 uint16 block sorts
+                                                   // < 185 000); a longer stream that does need kMaxCuts entries or
+                                                   // more is flagged for the host library (bwt_bucket)
 
 // chunk lists: [3] <= kTinyCap, [0] <= kSmallCap, [1] <= kBigCap, [2] larger
 // (rocPRIM segmented sort)
@@ -1093,6 +1098,15 @@ __global__ __launch_bounds__(kBucketThreads) __attribute__((amdgpu_waves_per_eu(
     for (uint32_t w = 0; w < kBucketThreads / 64; ++w) {
         if (w < wave) pcut += wcut[w];
         tcut += wcut[w];
+    }
+    // more cut entries than cuts[] (and the kBucketThreads lanes that turn
+    // them into chunks) hold: the chunks past the last kept entry would be
+    // one chunk of many buckets, which the segmented sort of the low key bits
+    // must never see.  The host library takes the stream; it gets no chunks,
+    // so nothing after this pass touches it (tcut is the same in every lane).
+    if (tcut >= kMaxCuts) {
+        if (t == 0) B.flags[s] |= kFlagHost;
+        return;
     }
     {
         uint32_t at = pcut + icut - ncut;
@@ -3718,6 +3732,7 @@ thread_local StageEvents t_stage;
 thread_local void (*t_hook)(void*, int) = nullptr;
 thread_local void* t_hook_ctx = nullptr;
 thread_local uint64_t t_last_blocks = 0;  // bzip2 blocks the calling thread's last call produced (lfm_hip_bzip2_last_blocks)
+thread_local uint32_t t_last_bwt[12] = {};  // the path its BWT took (lfm_hip_bzip2_last_bwt_stats)
 
 // rocPRIM temporary storage for the largest use of each primitive in a batch
 // of `count` streams (size queries only: no device work).  Carved out of the
@@ -3766,10 +3781,19 @@ struct Scratch {
     size_t tmp_bytes;
 };
 
-// What LFM_BZ2_STATS=1 reports about the BWT
+// What LFM_BZ2_STATS=1 reports about the BWT (its first_ties and left_runs)
+// and lfm_hip_bzip2_last_bwt_stats about the path bwt_sort took.  Every value is
+// a count the host has read back anyway or a host loop counter; chunks to
+// text_rounds are those of the last attempt (the one after a restart, if any).
 struct BwtStats {
-    uint32_t first_ties = 0;  // tied slots after the chunk sorts
-    uint32_t left_runs = 0;   // runs tie_runs_direct left
+    uint32_t chunks[4] = {};      // chunks per class: <= kTinyCap, <= kSmallCap, <= kBigCap, segmented sort
+    uint32_t first_ties = 0;      // tied slots after the chunk sorts
+    uint32_t left_runs = 0;       // runs tie_runs_direct left
+    uint32_t text_rounds = 0;     // text rounds run
+    uint32_t restarted = 0;       // the batch was sorted again with every rotation in the sort
+    uint32_t rank_form = 0;       // rank_rebuild: 0 not run, 1 bwt_rank0, 2 from the gathered group keys
+    uint32_t doubling_rounds = 0;
+    uint32_t flag_periodic = 0;   // bwt_flag_periodic ran
 };
 
 // The workspace, described once: every buffer in order, 256-byte aligned.
@@ -3911,6 +3935,11 @@ hipError_t first_round(const Batch& B, TieRounds& W)
         return e;
     hipLaunchKernelGGL(bwt_bucket<kBucketBits>, dim3(count), dim3(kBucketThreads), 0, st, B, CL);
     if ((e = hipGetLastError()) != hipSuccess || (e = W.read_count(nch, 24)) != hipSuccess) return e;
+    W.stats.chunks[0] = nch[5];
+    W.stats.chunks[1] = nch[0];
+    W.stats.chunks[2] = nch[1];
+    W.stats.chunks[3] = nch[2];
+    W.stats.first_ties = W.stats.left_runs = W.stats.text_rounds = 0;
     chunk_sorts<kTinyCap / kCsItems, kCsItems>(B, CL, 3, nch[5], st);
     chunk_sorts<kCsThreads, kCsItems>(B, CL, 0, nch[0], st);
     chunk_sorts<kBigThreads, kBigItems>(B, CL, 1, nch[1], st);
@@ -3971,6 +4000,7 @@ hipError_t text_rounds(const Batch& B, TieRounds& W)
         if (e != hipSuccess) return e;
         hipLaunchKernelGGL(text_write, dim3(grid), dim3(256), 0, st, B, W.cl, W.cnt);
         W.covered += tb;
+        ++W.stats.text_rounds;
         e = rocprim::select(W.tmp, W.tmp_bytes, B.keys_b, B.uflag, W.gk, W.cnt + 1, (size_t)cnt, st);
         if (e == hipSuccess) e = rocprim::select(W.tmp, W.tmp_bytes, W.cl, B.uflag, W.cl_next, W.cnt, (size_t)cnt, st);
         if (e != hipSuccess) return e;
@@ -3990,8 +4020,10 @@ hipError_t rank_rebuild(const Batch& B, TieRounds& W, uint32_t cnt)
     const uint32_t grid = list_grid(cnt);
     if (W.covered == kKeyBytes) gsrc = (uint64_t*)B.vals_b;  // cnt * 8 <= N * 4 when cnt <= N / 2: rank0 otherwise
     if (W.covered == kKeyBytes && (size_t)cnt * 2 > W.N) {
+        W.stats.rank_form = 1;
         hipLaunchKernelGGL(bwt_rank0, dim3(B.nstreams), dim3(1024), 0, st, B);
     } else {
+        W.stats.rank_form = 2;
         if (W.covered == kKeyBytes)
             hipLaunchKernelGGL(text_gather_keys, dim3(grid), dim3(256), 0, st, B, W.cl, W.cnt, gsrc);
         uint32_t* bnd2 = (uint32_t*)B.keys_a;  // 2 * cnt u32 fit the keys area
@@ -4022,6 +4054,7 @@ hipError_t doubling_rounds(const Batch& B, TieRounds& W)
         if (cnt == 0) break;
         if (h >= max_n) {  // every remaining tie is a pair of equal rotations
             hipLaunchKernelGGL(bwt_flag_periodic, dim3(256), dim3(256), 0, st, B, W.cl, W.cnt);
+            W.stats.flag_periodic = 1;
             break;
         }
         const uint32_t grid = list_grid(cnt);
@@ -4038,6 +4071,7 @@ hipError_t doubling_rounds(const Batch& B, TieRounds& W)
         if (e != hipSuccess) return e;
         std::swap(W.cl, W.cl_next);
         h *= 2;
+        ++W.stats.doubling_rounds;
     }
     return hipSuccess;
 }
@@ -4060,7 +4094,10 @@ hipError_t bwt_sort(Batch& B, const Scratch& S, hipStream_t st, BwtStats* stats)
             W.none_left = true;
             break;
         }
-        if (!B.it_full) continue;  // doubling needs the rank of every rotation: sort them all
+        if (!B.it_full) {  // doubling needs the rank of every rotation: sort them all
+            W.stats.restarted = 1;
+            continue;
+        }
         if ((e = rank_rebuild(B, W, cnt)) != hipSuccess) return e;
         break;
     }
@@ -4161,6 +4198,12 @@ int bzip2_blocks(const void* d_img, const uint32_t dims[5], const uint32_t bs[5]
     // placed by bwt_induce unless bwt_sort had to sort them all (B.it_full)
     BwtStats bwt_stats;
     if (bwt_sort(B, S, st, &bwt_stats) != hipSuccess) return LFM_HIP_ERUNTIME;
+    {
+        const uint32_t v[12] = {bwt_stats.chunks[0], bwt_stats.chunks[1], bwt_stats.chunks[2], bwt_stats.chunks[3],
+                                bwt_stats.first_ties, bwt_stats.left_runs, bwt_stats.text_rounds, bwt_stats.restarted,
+                                bwt_stats.rank_form, bwt_stats.doubling_rounds, bwt_stats.flag_periodic, 0u};
+        std::copy(v, v + 12, t_last_bwt);
+    }
     if (!B.it_full) {
         // the other type placed by one scan, which writes the symbols ll[]
         B.ent = (uint2*)B.keys_a;
@@ -4288,6 +4331,11 @@ extern "C" void lfm_hip_bzip2_set_stage_hook(void (*fn)(void*, int), void* ctx)
 }
 
 extern "C" uint64_t lfm_hip_bzip2_last_blocks(void) { return t_last_blocks; }
+
+extern "C" void lfm_hip_bzip2_last_bwt_stats(uint32_t out[12])
+{
+    if (out) std::copy(t_last_bwt, t_last_bwt + 12, out);
+}
 
 extern "C" int lfm_hip_bzip2_last_stage_ms(float ms[5])
 {

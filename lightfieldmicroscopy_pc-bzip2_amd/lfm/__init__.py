@@ -50,7 +50,7 @@ EXPORTS = [
     "lfm_hip_synth", "lfm_hip_device_count", "lfm_hip_force_generic", "lfm_hip_bzip2_workspace_bytes", "lfm_hip_bzip2_out_cap",
     "lfm_hip_bzip2_blocks", "lfm_hip_bzip2_last_stage_ms", "lfm_hip_bunzip2_workspace_bytes", "lfm_hip_bunzip2_blocks", "lfm_hip_scatter_blocks",
     "lfm_hip_crop_region", "lfm_hip_bzip2_workspace_bytes_multi", "lfm_hip_bzip2_max_count_multi",
-    "lfm_hip_bzip2_blocks_multi", "lfm_hip_bzip2_last_blocks",
+    "lfm_hip_bzip2_blocks_multi", "lfm_hip_bzip2_last_blocks", "lfm_hip_bzip2_last_bwt_stats",
     "lfm_hip_bunzip2_max_parts", "lfm_hip_bunzip2_workspace_bytes_multi", "lfm_hip_bunzip2_blocks_multi",
     "lfm_hip_bunzip2_issue_multi", "lfm_hip_bunzip2_set_periodic", "lfm_hip_bunzip2_get_periodic",
 ]
@@ -190,6 +190,8 @@ def lib():
     L.lfm_hip_bzip2_blocks_multi.argtypes = L.lfm_hip_bzip2_blocks.argtypes
     L.lfm_hip_bzip2_last_blocks.argtypes = []
     L.lfm_hip_bzip2_last_blocks.restype = ctypes.c_uint64
+    L.lfm_hip_bzip2_last_bwt_stats.argtypes = [u32p]
+    L.lfm_hip_bzip2_last_bwt_stats.restype = None
     L.lfm_set_bzip2_multiblock.argtypes = [ctypes.c_int]
     L.lfm_get_bzip2_multiblock.argtypes = []
     L.lfm_encoder_stream_counts.argtypes = [vp] + [ctypes.POINTER(ctypes.c_uint64)] * 3
@@ -973,6 +975,18 @@ def bzip2_device(d_img, dims, block, bpp, level=None, first=0, count=None, strea
             out.append(host[o:o + sizes[i]])
             o += sizes[i]
     return out, list(flags)
+
+
+BWT_STATS = ("chunks_tiny", "chunks_small", "chunks_big", "chunks_segmented", "first_ties", "left_runs",
+             "text_rounds", "restarted", "rank_form", "doubling_rounds", "flag_periodic")
+
+
+def bzip2_last_bwt_stats():
+    """The path the BWT sort of this thread's last bzip2_device call took
+    (lfm_hip_bzip2_last_bwt_stats, lfm_hip.h), as a dict over BWT_STATS."""
+    out = (ctypes.c_uint32 * 12)()
+    lib().lfm_hip_bzip2_last_bwt_stats(out)
+    return dict(zip(BWT_STATS, list(out)))
 
 
 def set_bunzip2_multiblock(on):
