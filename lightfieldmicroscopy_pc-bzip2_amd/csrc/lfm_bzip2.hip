@@ -2231,9 +2231,9 @@ __global__ __launch_bounds__(64) void bwt_induce(Batch B)
 //   mtf_last    per segment: the sorted symbols ll[j] (inUse-mapped bytes
 //               before each sorted rotation) and each symbol's last position
 //   mtf_prefix  per stream: exclusive running max over the segments
-//   mtf_seg     per segment, one wave: initial list from the ranks of those
-//               positions, then the sequential MTF (list packed 4 entries per
-//               lane; lookups by ballot, shifts by a one-lane wave rotate)
+//   mtf_win     per segment, one wave: initial list from the ranks of those
+//               positions (a bitonic sort in registers), then the MTF of the
+//               segment's run heads in windows of 64 (below)
 //   rle2        per stream: zero runs -> RUNA/RUNB digits, v -> v + 1, EOB,
 //               symbol frequencies (the run state is carried across thread
 //               chunks by a scan, as in rle1_crc)
@@ -2324,10 +2324,26 @@ __global__ __launch_bounds__(256) void mtf_prefix(Batch B, uint32_t nseg_max, in
     }
 }
 
-// Window-parallel MTF (the default): one wave per 4096-symbol segment walks it
-// in windows of 64 positions, one lane per position, with the list state
-// (P = place of each symbol, L = symbol at each place) in LDS.  For position
-// l of a window whose symbol c occurred earlier in the window at p:
+// Window-parallel MTF (the default): one wave per 4096-symbol segment, with
+// the list state (P = place of each symbol, L = symbol at each place) in LDS.
+// A position whose symbol equals the one before it has value 0 and leaves the
+// list alone, so only the run heads are walked (the segment's first position
+// and every position whose symbol differs from its predecessor's; about 55 %
+// of the column of 16-bit pixels, whose low bytes follow a high byte that
+// seldom changes).  The column is read in loads of 64 positions.  Of a load
+// with fewer than kMtfDense heads the others store their 0 at once and the
+// heads go into a ring in LDS (symbol and segment offset, slots by ballot and
+// mbcnt); whenever the ring holds 64 heads the 64 oldest make a window, one
+// lane per head, and what is left at the segment's end makes a last, partial
+// window.  A load with kMtfDense heads or more is a window as it stands, its
+// few repeats included, after the ring has been emptied into a window of its
+// own: compacting such a load costs more than its repeats save, and a column
+// without runs never touches the ring (the dense half of every stream of
+// pixels does not either).  Walking every load's heads through the ring, as
+// first built, measured 1.78 ms per launch against the parent's 1.77 on
+// config-3 symbols and 2.61 against 2.25 on random bytes.  A value goes to
+// its lane's own position, so no store leaves [js, je).  For lane l of a
+// window whose symbol c occurred earlier in the window at lane p:
 //     m = number of distinct symbols at positions (p, l),
 // otherwise (first occurrence in the window)
 //     m = P(c) + number of distinct earlier window symbols d with P(d) > P(c),
@@ -2370,12 +2386,79 @@ __device__ __forceinline__ uint64_t wave_or_scan_excl(uint64_t x)
     return ((uint64_t)wave_or_scan_excl32((uint32_t)(x >> 32)) << 32) | wave_or_scan_excl32((uint32_t)x);
 }
 
+constexpr uint32_t kMtfDense = 48;  // heads from which a load is a window as it stands
+constexpr uint32_t kMtfRing = 128;  // at most 63 heads pending plus kMtfDense - 1 of a load
+
+// Bitonic sort of 256 words over a wave, ascending: element i = 4 lane + q.
+// x of lane ^ M (M a power of two): DPP where one row holds both lanes,
+// ds_swizzle inside 32 lanes, ds_bpermute across the halves.  Every lane active.
+template <uint32_t M>
+__device__ __forceinline__ uint32_t lane_xor(uint32_t x)
+{
+    if constexpr (M == 1) return dpp_get<0xB1, 0xF>(x);        // quad_perm:[1,0,3,2]
+    else if constexpr (M == 2) return dpp_get<0x4E, 0xF>(x);   // quad_perm:[2,3,0,1]
+    else if constexpr (M == 8) return dpp_get<0x128, 0xF>(x);  // row_ror:8
+    else if constexpr (M == 4 || M == 16) return (uint32_t)__builtin_amdgcn_ds_swizzle((int)x, (int)((M << 10) | 0x1Fu));  // xor M
+    else return (uint32_t)__shfl_xor((int)x, (int)M);
+}
+__device__ __forceinline__ void cmpx(uint32_t& a, uint32_t& b)
+{
+    const uint32_t lo = min(a, b), hi = max(a, b);
+    a = lo;
+    b = hi;
+}
+template <uint32_t M>
+__device__ __forceinline__ void bitonic_lanes(uint32_t (&x)[4], uint32_t lane)
+{
+    const bool low = (lane & M) == 0;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const uint32_t y = lane_xor<M>(x[q]);
+        x[q] = low ? min(x[q], y) : max(x[q], y);
+    }
+}
+// merges the sorted runs of K / 2 elements into runs of K, alternately up and
+// down (all up for K = 256): a run that goes down sorts its complements up
+template <uint32_t K>
+__device__ __forceinline__ void bitonic_merge(uint32_t (&x)[4], uint32_t lane)
+{
+    const uint32_t f = (K < 256 && (4 * lane & K)) ? ~0u : 0u;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) x[q] ^= f;
+    if constexpr (K >= 256) bitonic_lanes<32>(x, lane);
+    if constexpr (K >= 128) bitonic_lanes<16>(x, lane);
+    if constexpr (K >= 64) bitonic_lanes<8>(x, lane);
+    if constexpr (K >= 32) bitonic_lanes<4>(x, lane);
+    if constexpr (K >= 16) bitonic_lanes<2>(x, lane);
+    if constexpr (K >= 8) bitonic_lanes<1>(x, lane);
+    cmpx(x[0], x[2]);
+    cmpx(x[1], x[3]);
+    cmpx(x[0], x[1]);
+    cmpx(x[2], x[3]);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) x[q] ^= f;
+}
+__device__ __forceinline__ void bitonic_sort256(uint32_t (&x)[4], uint32_t lane)
+{
+    cmpx(x[0], x[1]);
+    cmpx(x[3], x[2]);
+    bitonic_merge<4>(x, lane);
+    bitonic_merge<8>(x, lane);
+    bitonic_merge<16>(x, lane);
+    bitonic_merge<32>(x, lane);
+    bitonic_merge<64>(x, lane);
+    bitonic_merge<128>(x, lane);
+    bitonic_merge<256>(x, lane);
+}
+
 __global__ __launch_bounds__(256) void mtf_win(Batch B, uint32_t nseg_max, const int32_t* __restrict__ seg_last)
 {
-    __shared__ int32_t key[4][256];
     __shared__ uint64_t mt[4][256];
     __shared__ uint8_t Pt[4][256], Lt[4][256], inw[4][256];
-    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    __shared__ uint32_t ring[4][kMtfRing];  // pending heads: symbol | segment offset << 8
+    const uint32_t lane = threadIdx.x & 63;
+    // (in a scalar register: the segment's bounds and the loop below branch on it)
+    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const uint32_t s = blockIdx.y, k = blockIdx.x * 4 + wave;
     if (B.flags[s] & kFlagHost) return;
     const uint32_t n = B.n[s];
@@ -2385,35 +2468,38 @@ __global__ __launch_bounds__(256) void mtf_win(Batch B, uint32_t nseg_max, const
     uint32_t nin = 0;
     for (int q = 0; q < 8; ++q) nin += __popc(B.inuse[s * 8 + q]);
     // list at js: seen symbols by last position (descending), then the unseen
-    // ones by symbol index (ascending) -- key(unseen c) = -1 - c
+    // ones by symbol index (ascending) -- key(unseen c) = -1 - c.  The keys
+    // are distinct, so the place of a symbol is its rank in the sorted order
+    // of (key descending): one word per symbol, the complemented key above
+    // the symbol (key + 256 < 2^23: a block holds under 2^20 positions), the
+    // words of the symbols not in use last, sorted in registers
     const int32_t* lb = seg_last + ((size_t)s * nseg_max + k) * 256;
-    for (uint32_t c = lane; c < 256; c += 64) {
-        const int32_t v = c < nin ? lb[c] : INT32_MIN;
-        key[wave][c] = (c < nin && v < 0) ? -1 - (int32_t)c : v;
-        inw[wave][c] = 0;
+    const int4 lv = *(const int4*)(lb + 4 * lane);
+    const int32_t lq[4] = {lv.x, lv.y, lv.z, lv.w};
+    uint32_t x[4];
+#pragma unroll
+    for (uint32_t q = 0; q < 4; ++q) {
+        const uint32_t c = 4 * lane + q;
+        const int32_t key = lq[q] < 0 ? -1 - (int32_t)c : lq[q];
+        x[q] = c < nin ? ((0x7FFFFFu - (uint32_t)(key + 256)) << 8) | c : ~0u;
     }
-    wsync();
-    for (uint32_t c = lane; c < nin; c += 64) {
-        const int32_t kc = key[wave][c];
-        uint32_t r = 0;
-        for (uint32_t d = 0; d < nin; ++d) r += key[wave][d] > kc ? 1u : 0u;
-        Pt[wave][c] = (uint8_t)r;
-        Lt[wave][r] = (uint8_t)c;
+    for (uint32_t c = lane; c < 256; c += 64) inw[wave][c] = 0;
+    bitonic_sort256(x, lane);
+#pragma unroll
+    for (uint32_t q = 0; q < 4; ++q) {
+        const uint32_t p = 4 * lane + q, c = x[q] & 0xFFu;
+        if (p < nin) {
+            Lt[wave][p] = (uint8_t)c;
+            Pt[wave][c] = (uint8_t)p;
+        }
     }
     wsync();
     const uint8_t* llbuf = (const uint8_t*)B.mtfv + o;
     uint8_t* mraw = B.uflag + o;
     const uint32_t je = min(n, js + kSeg);
     const uint64_t lt = (1ull << lane) - 1ull, gt = ~lt & ~(1ull << lane);
-    // the next window's symbol is loaded a window ahead, unconditionally (a
-    // clamped index): a load under a branch made the compiler wait for every
-    // outstanding load at the next use
-    uint32_t cn = llbuf[min(js + lane, je - 1)];
-    for (uint32_t j0 = js; j0 < je; j0 += 64) {
-        const uint32_t j = j0 + lane;
-        const bool valid = j < je;
-        const uint32_t c = valid ? cn : 0u;
-        cn = llbuf[min(j + 64, je - 1)];
+    // one window: lane l holds the head with symbol c at segment offset off
+    auto window = [&](const uint32_t c, const uint32_t off, const bool valid) {
         // match mask of c in this window
         if (valid) mt[wave][c] = 0;
         wsync();
@@ -2455,7 +2541,7 @@ __global__ __launch_bounds__(256) void mtf_win(Batch B, uint32_t nseg_max, const
             }
             if (isF) m += cnt;
         }
-        if (valid) mraw[j] = (uint8_t)m;
+        if (valid) mraw[js + off] = (uint8_t)m;  // off is a valid lane's own position: js + off < je
         // list update: window symbols by last occurrence, then the rest.  The
         // window symbols' old places (their first occurrences' P0) are below
         // 32 * (whi + 1), and every entry past them keeps its place (nw
@@ -2499,6 +2585,73 @@ __global__ __launch_bounds__(256) void mtf_win(Batch B, uint32_t nseg_max, const
         }
         if (isF) inw[wave][P0] = 0;
         wsync();
+    };
+    // The symbols of four loads (256 positions) are fetched four loads ahead,
+    // unconditionally (clamped indices: a load under a branch made the
+    // compiler wait for every outstanding load at the next use): a sparse
+    // load is too short to hide a fetch issued one load earlier.  Byte q of
+    // lane l is position jg + 64 q + l.
+    uint32_t nq[4];
+    auto fetch = [&](const uint32_t jg) {
+#pragma unroll
+        for (uint32_t q = 0; q < 4; ++q) nq[q] = llbuf[min(jg + 64u * q + lane, je - 1)];
+    };
+    fetch(js);
+    uint32_t cur = 0;         // the symbols of the four loads in hand, a byte each
+    uint32_t plast = 0;       // the previous load's last symbol
+    uint32_t wr = 0, rd = 0;  // ring entries written and taken (wave-uniform): wr - rd < 128
+    uint32_t j0 = js;         // the next load (wave-uniform)
+    uint32_t c = 0;           // the load in hand: this lane's symbol
+    bool valid = false, held = false;  // held: a dense load waits until the ring is empty
+    for (;;) {
+        if (!held && j0 < je) {
+            const uint32_t q = ((j0 - js) >> 6) & 3u;
+            if (q == 0) {
+                cur = nq[0] | (nq[1] << 8) | (nq[2] << 16) | (nq[3] << 24);
+                fetch(j0 + 256);
+            }
+            const uint32_t j = j0 + lane;
+            valid = j < je;
+            c = valid ? (cur >> (8u * q)) & 0xFFu : 0u;
+            const uint32_t pd = dpp_get<0x138, 0xF>(c);  // wave_shr:1, every lane active
+            const uint32_t pv = lane ? pd : plast;
+            plast = (uint32_t)__builtin_amdgcn_readlane((int)c, 63);
+            const bool head = valid && (j == js || c != pv);
+            const uint64_t H = ballot64(head);
+            const uint32_t nh = (uint32_t)__popcll(H);
+            if (nh >= kMtfDense) {
+                held = true;
+            } else {
+                if (valid && !head) mraw[j] = 0;
+                if (head) ring[wave][(wr + (uint32_t)__popcll(H & lt)) % kMtfRing] = c | ((j - js) << 8);
+                wr += nh;
+                j0 += 64;
+            }
+        }
+        const uint32_t cnt = wr - rd;
+        const bool direct = held && cnt == 0;
+        if (!direct && !held && cnt < 64 && !(j0 >= je && cnt)) {
+            if (j0 >= je) break;
+            continue;
+        }
+        uint32_t wc, woff;
+        bool wvalid;
+        if (direct) {  // the load as it stands, its repeats included (they come out as 0)
+            wc = c;
+            woff = j0 + lane - js;
+            wvalid = valid;
+            held = false;
+            j0 += 64;
+        } else {  // the 64 oldest heads; all of them before a dense load and at the segment's end
+            const uint32_t take = min(cnt, 64u);
+            wsync();
+            const uint32_t e = ring[wave][(rd + lane) % kMtfRing];  // lanes >= take: a stale entry, unused
+            wvalid = lane < take;
+            wc = wvalid ? e & 0xFFu : 0u;
+            woff = e >> 8;
+            rd += take;
+        }
+        window(wc, woff, wvalid);
     }
 }
 
