@@ -137,6 +137,13 @@ uint64_t lfm_hip_bzip2_last_blocks(void);
  * run, [10] 1 when streams still tied after the last round were flagged as
  * periodic, [11] 0. */
 void lfm_hip_bzip2_last_bwt_stats(uint32_t out[12]);
+/* How the sorted rotations of the calling thread's last lfm_hip_bzip2_blocks
+ * or lfm_hip_bzip2_blocks_multi were placed in the final order (read-only,
+ * decided from the counts above): 0 not at all (the batch was sorted again
+ * with every rotation in the sort), 1 by the chunk sorts themselves, 2 by the
+ * placement kernel over the whole batch (segmented chunks, or a tied run left
+ * to the text rounds). */
+uint32_t lfm_hip_bzip2_last_place_path(void);
 /* Stage times (HIP events on its stream, ms) of the calling thread's last
  * lfm_hip_bzip2_blocks / lfm_hip_bzip2_blocks_multi: [0] RLE1 + CRC, [1] BWT (buckets, chunk sorts, tie
  * rounds), [2] MTF + RUNA/RUNB, [3] Huffman tables, [4] bit emission +

@@ -20,7 +20,7 @@
 //           are sorted (bwt_bucket, chunk sorts by the 8-byte prefix, text
 //           rounds over what still ties; prefix doubling over every rotation
 //           only for long repeats), the others placed by one induction scan
-//           (bwt_place_sorted, bwt_induce).  A periodic block (equal
+//           (the sorts' own placement or bwt_place_sorted, then bwt_induce).  A periodic block (equal
 //           rotations) is handed back to the host library.
 //   mtf     compress.c generateMTFValues: move-to-front per 4096-symbol
 //           segment (mtf_last, mtf_prefix, mtf_win), then RUNA/RUNB zero runs
@@ -143,8 +143,8 @@ struct Batch {
     uint32_t* nsub;          // rotations sorted per stream (the A or B rotations, or all of them)
     uint32_t* bwt_mode;      // per stream: kModeSortA / kModeSortB / kModeFull
     uint32_t* abcnt;         // per stream: A rotations per first byte [256], then B rotations [256]
-    uint32_t* itab;          // per stream: tq, cs, cl, s0 [256] each (bwt_bucket, for bwt_place_sorted / bwt_induce)
-    uint2* ent;              // bwt_induce's entries per compact scan index (the keys_a area, free after the sorts)
+    uint32_t* itab;          // per stream: tq, cs, cl, s0 [256] each (bwt_bucket, for the placement and bwt_induce)
+    uint2* ent;              // bwt_induce's entries per compact scan index (the keys_a area: only the segmented sort and the tie rounds use it)
     uint32_t it_full;        // sort every rotation (no induction): the fallback for ties that need doubling
     // streams of several bzip2 blocks (lfm_hip_bzip2_blocks_multi): a stream
     // owns `parts` consecutive slots, one per bzip2 block ("part") libbzip2
@@ -1338,6 +1338,125 @@ __global__ __launch_bounds__(256) void tie_runs_direct(Batch B, const uint32_t* 
     }
 }
 
+__device__ __forceinline__ void make_u2s(const Batch& B, uint32_t s, uint8_t* u2s, uint32_t lane, uint32_t* nin_out)
+{
+    uint32_t inu[8], nin = 0;
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+        inu[q] = B.inuse[s * 8 + q];
+        nin += __popc(inu[q]);
+    }
+    for (uint32_t c = lane; c < 256; c += 64) {
+        uint32_t below = 0;
+        for (uint32_t q = 0; q < (c >> 5); ++q) below += __popc(inu[q]);
+        below += __popc(inu[c >> 5] & ((1u << (c & 31)) - 1u));
+        u2s[c] = (uint8_t)below;
+    }
+    *nin_out = nin;
+}
+
+// ------------------------------------------------------------ placement --
+// One sorted rotation placed: the one statement of what "induction" below
+// says about a sorted slot (the final order, `ent`, itab).  Three callers: the
+// chunk sorts' epilogue (PLACE), which holds the rotation when it is sorted;
+// bwt_place_tied, over the slots tie_runs_direct re-ordered; bwt_place_sorted,
+// over every slot of the batch, for the calls that leave the common path.
+constexpr uint32_t kIndPend = 0xFFFFFFFFu;  // never an entry: nprev <= 3
+constexpr uint32_t kIndIdx = 0xFFFFFu;      // n < nblock_max < 2^20
+constexpr uint32_t kIndPlaced = 1u << 23;
+
+// A stream's placement tables in LDS: tq, s0 (itab), cb[c] the compact index
+// of bucket c's first sorted rotation (kModeSortA: the ranks count down from
+// it), and the byte -> symbol map.
+struct PlaceTabs {
+    uint32_t tq_[256], s0_[256], cb_[256];
+    uint8_t u2s_[256];
+    __device__ __forceinline__ uint32_t tq(uint32_t c) const { return tq_[c]; }
+    __device__ __forceinline__ uint32_t s0(uint32_t c) const { return s0_[c]; }
+    __device__ __forceinline__ uint32_t cb(uint32_t c) const { return cb_[c]; }
+    __device__ __forceinline__ uint32_t sym(uint32_t b) const { return u2s_[b]; }
+};
+
+// compact index of bucket c's first sorted rotation (an empty sorted part: never used)
+__device__ __forceinline__ uint32_t place_cb(const uint32_t* __restrict__ it, const uint32_t* __restrict__ ab, bool rev,
+                                            uint32_t c)
+{
+    const uint32_t u = rev ? 255u - c : c;
+    return it[256 + u] + it[512 + u] + (rev ? ab[c] - 1u : 0u);
+}
+
+// by threads 0 .. 255 of a workgroup (the first wave also builds the symbol
+// map); the caller's barrier publishes the tables
+__device__ __forceinline__ void place_tabs_load(const Batch& B, uint32_t s, uint32_t mode, PlaceTabs& P, uint32_t t)
+{
+    if (t < 64) {
+        uint32_t nin;
+        make_u2s(B, s, P.u2s_, t, &nin);
+    }
+    if (t < 256) {
+        const uint32_t* it = B.itab + (size_t)s * 1024;
+        P.tq_[t] = it[t];
+        P.s0_[t] = it[768 + t];
+        P.cb_[t] = place_cb(it, B.abcnt + (size_t)s * 512, mode == kModeSortA, t);
+    }
+}
+
+// the same tables read where they lie, for the few slots of bwt_place_tied
+struct PlaceTabsGlobal {
+    const uint32_t* it;
+    const uint32_t* ab;
+    const uint32_t* inuse;
+    bool rev;
+    __device__ __forceinline__ uint32_t tq(uint32_t c) const { return it[c]; }
+    __device__ __forceinline__ uint32_t s0(uint32_t c) const { return it[768 + c]; }
+    __device__ __forceinline__ uint32_t cb(uint32_t c) const { return place_cb(it, ab, rev, c); }
+    __device__ __forceinline__ uint32_t sym(uint32_t b) const
+    {
+        uint32_t below = __popc(inuse[b >> 5] & ((1u << (b & 31)) - 1u));
+        for (uint32_t q = 0; q < (b >> 5); ++q) below += __popc(inuse[q]);
+        return below;
+    }
+};
+
+// T[i-4 .. i] of rotation i: two aligned dwords at a clamped address (the
+// first four rotations wrap and read byte by byte), so that a caller can
+// issue the loads of all its rotations before it uses any.
+__device__ __forceinline__ const uint32_t* place_text_at(const uint8_t* __restrict__ T, uint32_t i)
+{
+    return (const uint32_t*)(T + ((i >= 4 ? i - 4 : 0u) & ~3u));
+}
+// x = T[i-4] | T[i-3] << 8 | T[i-2] << 16 | T[i-1] << 24, c = T[i]
+__device__ __forceinline__ void place_text(const uint8_t* __restrict__ T, uint32_t n, uint32_t i, uint32_t w0, uint32_t w1,
+                                           uint32_t& x, uint32_t& c)
+{
+    if (i >= 4) {
+        const uint32_t sh = ((i - 4) & 3u) * 8u;
+        const uint64_t d = (uint64_t)w0 | ((uint64_t)w1 << 32);
+        x = (uint32_t)(d >> sh);
+        c = (uint32_t)(d >> (sh + 32)) & 0xFFu;
+    } else {
+        x = 0;
+        for (uint32_t r = 1; r <= 4; ++r) x |= (uint32_t)T[(i + 4 * n - r) % n] << (32 - 8 * r);
+        c = T[i];
+    }
+}
+
+// Sorted slot j of a stream (value v = i | T[i-1] << 24, x and c as above):
+// its final position is known, so the symbol goes to LL there, origPtr is
+// that position for rotation 0, and (unless the stream is sorted whole) the
+// entry goes to its compact index, counted from cb[c] in the scan's direction.
+template <class Tabs>
+__device__ __forceinline__ void place_slot(const Tabs& P, uint32_t mode, uint32_t j, uint32_t v, uint32_t x, uint32_t c,
+                                           uint8_t* __restrict__ LL, uint2* __restrict__ E, uint32_t* __restrict__ orig_ptr)
+{
+    const uint32_t r = j - P.s0(c), qq = P.tq(c) + r;
+    LL[qq] = (uint8_t)P.sym(v >> 24);
+    if ((v & kIdxMask) == 0) *orig_ptr = qq;
+    if (mode != kModeFull)
+        E[mode == kModeSortA ? P.cb(c) - r : P.cb(c) + r] =
+            make_uint2(v | (3u << 20), ((x >> 16) & 0xFFu) | (((x >> 8) & 0xFFu) << 8) | ((x & 0xFFu) << 16) | (c << 24));
+}
+
 // Thread t's items of chunk [cb, cb + m), striped (item q is slot q * TH + t:
 // coalesced): the values and their 8-byte keys rebuilt from the text; items
 // past m get key ~0, value 0.  Every load is unconditional (clamped
@@ -1384,7 +1503,15 @@ __device__ __forceinline__ void chunk_load(const Batch& B, uint32_t cb, uint32_t
 // neighbours in registers (each thread's edge keys through LDS), and sa /
 // uflag go back striped through LDS.  The sorted keys are not stored: the few
 // consumers (tie groups) recompute them from the text (rot_key8).
-template <int TH, int IPT>
+//
+// PLACE: the workgroup also places its rotations (place_slot) from the blocked
+// arrangement, where it holds each one's value, its sorted slot and T[i] (the
+// key's top byte); the stream's tables are loaded into LDS ahead of the sort
+// (a chunk never spans streams).  T[i-4 .. i-2] are read again after the sort
+// and not carried through it: a second value word would make rocPRIM's merge
+// passes move 8-byte values.  Tied slots are placed in the provisional order;
+// bwt_place_tied places them again once tie_runs_direct has ordered them.
+template <int TH, int IPT, bool PLACE>
 __global__ __launch_bounds__(TH) void bwt_chunk_sort(Batch B, const uint32_t* __restrict__ cbp,
                                                      const uint32_t* __restrict__ cep, uint32_t nch, uint32_t per)
 {
@@ -1409,7 +1536,10 @@ __global__ __launch_bounds__(TH) void bwt_chunk_sort(Batch B, const uint32_t* __
         typename ExV::storage_type ev;
         Xch x;
     } sm;
+    __shared__ std::conditional_t<PLACE, PlaceTabs, char> P;
     const uint32_t cb = cbp[c], ce = cep[c], m = ce - cb, t = threadIdx.x;
+    const uint32_t s = cb / B.cap, mode = PLACE ? B.bwt_mode[s] : 0u;
+    if constexpr (PLACE) place_tabs_load(B, s, mode, P, t);  // (published by the barriers of the sort)
     uint64_t k[IPT];
     uint32_t v[IPT];
     chunk_load<TH, IPT>(B, cb, m, t, k, v);
@@ -1444,9 +1574,33 @@ __global__ __launch_bounds__(TH) void bwt_chunk_sort(Batch B, const uint32_t* __
         else *(uint32_t*)&sm.x.fl[t * IPT] = (uint32_t)fpack;
     }
     __syncthreads();
+    [[maybe_unused]] const uint8_t* T = B.T + (size_t)s * B.cap;
+    [[maybe_unused]] uint32_t w0[IPT], w1[IPT];
+    if constexpr (PLACE) {  // (items past m hold value 0: the loads stay inside the text)
+#pragma unroll
+        for (int q = 0; q < IPT; ++q) {
+            const uint32_t* w = place_text_at(T, v[q] & kIdxMask);
+            w0[q] = w[0];
+            w1[q] = w[1];
+        }
+    }
     for (uint32_t j = t; j < m; j += TH) {
         B.sa[cb + j] = sm.x.sv[j];
         B.uflag[cb + j] = sm.x.fl[j];
+    }
+    if constexpr (PLACE) {
+        const size_t o = (size_t)s * B.cap;
+        const uint32_t n = B.n[s], j0 = cb - (uint32_t)o + t * IPT;
+        uint8_t* LL = (uint8_t*)B.mtfv + o;
+        uint2* E = B.ent + o;
+#pragma unroll
+        for (int q = 0; q < IPT; ++q) {
+            if (t * IPT + q < m) {
+                uint32_t x, ci;
+                place_text(T, n, v[q] & kIdxMask, w0[q], w1[q], x, ci);
+                place_slot(P, mode, j0 + q, v[q], x, (uint32_t)(k[q] >> 56), LL, E, B.orig_ptr + s);
+            }
+        }
     }
     if (__any(nt)) {
         for (int d = 32; d > 0; d >>= 1) nt += __shfl_xor(nt, d);
@@ -1768,25 +1922,8 @@ __global__ __launch_bounds__(256) void bwt_flag_periodic(Batch B, const uint32_t
         atomicOr(&B.flags[cl[c] / B.cap], kFlagHost);
 }
 
-__device__ __forceinline__ void make_u2s(const Batch& B, uint32_t s, uint8_t* u2s, uint32_t lane, uint32_t* nin_out)
-{
-    uint32_t inu[8], nin = 0;
-#pragma unroll
-    for (int q = 0; q < 8; ++q) {
-        inu[q] = B.inuse[s * 8 + q];
-        nin += __popc(inu[q]);
-    }
-    for (uint32_t c = lane; c < 256; c += 64) {
-        uint32_t below = 0;
-        for (uint32_t q = 0; q < (c >> 5); ++q) below += __popc(inu[q]);
-        below += __popc(inu[c >> 5] & ((1u << (c & 31)) - 1u));
-        u2s[c] = (uint8_t)below;
-    }
-    *nin_out = nin;
-}
-
 // ------------------------------------------------------------ induction --
-// bwt_place_sorted + bwt_induce: the final order from the sorted rotations.
+// Placement (above) + bwt_induce: the final order from the sorted rotations.
 // In the final order (position q) bucket c (first byte c) holds its A
 // rotations, then its B rotations.  One type is sorted (sa); the other is
 // placed by one scan: kModeSortB scans left to right placing the A rotations,
@@ -1798,8 +1935,8 @@ __device__ __forceinline__ void make_u2s(const Batch& B, uint32_t s, uint8_t* u2
 //
 // The output is ll[]: at every final position the symbol of the byte before
 // its rotation, and origPtr, the position of rotation 0.  Whoever places a
-// rotation holds that byte and writes the symbol there: bwt_place_sorted for
-// the sorted rotations, bwt_induce for each rotation it induces.
+// rotation holds that byte and writes the symbol there: place_slot for the
+// sorted rotations, bwt_induce for each rotation it induces.
 //
 // A placed rotation p induces in its turn only when p - 1 is placed too, by
 // the rule above when T[p-1]' >= T[p]': it is "live".  The others are dead:
@@ -1815,15 +1952,13 @@ __device__ __forceinline__ void make_u2s(const Batch& B, uint32_t s, uint8_t* u2
 // hi = T[i-2] | T[i-3] << 8 | T[i-4] << 16 | T[i] << 24: nprev of the three
 // bytes before T[i-1] are valid (3 for a sorted rotation, one fewer per
 // induction: a longer chain of placed rotations reads the text), and T[i] is
-// the rotation's bucket.  bwt_place_sorted writes the sorted entries and
-// kIndPend into the live slots; bwt_induce fills those as it goes.
+// the rotation's bucket.  place_slot writes the sorted entries; the live slots
+// start as kIndPend (bwt_pend_live, or bwt_place_sorted where it runs) and
+// bwt_induce fills them as it goes.
 //
 // itab (bwt_bucket), 256 words each: tq[c] the final position of bucket c's
 // first sorted rotation, cs[u], cl[u], and s0[c] the sa slot of bucket c's
 // first sorted rotation.
-constexpr uint32_t kIndPend = 0xFFFFFFFFu;  // never an entry: nprev <= 3
-constexpr uint32_t kIndIdx = 0xFFFFFu;      // n < nblock_max < 2^20
-constexpr uint32_t kIndPlaced = 1u << 23;
 constexpr uint32_t kPlaceChunk = 2048;  // (1 024, 4 096, 8 192 equal or slower end to end)  // sorted slots / positions per bwt_place_sorted workgroup
 
 // One workgroup per kPlaceChunk sorted slots and compact scan indices of a
@@ -1832,29 +1967,16 @@ constexpr uint32_t kPlaceChunk = 2048;  // (1 024, 4 096, 8 192 equal or slower 
 // should stay in one L2 while its chunks run.
 __global__ __launch_bounds__(256) void bwt_place_sorted(Batch B, uint32_t chunks)
 {
-    __shared__ uint32_t tq[256], cs[256], cl[256], s0[256];
-    __shared__ uint32_t cb[256];  // compact index of bucket c's first sorted rotation (kModeSortA: the ranks count down from it)
-    __shared__ uint8_t u2s[256];
+    __shared__ PlaceTabs P;
+    __shared__ uint32_t cs[256], cl[256];
     const uint32_t t = threadIdx.x, k = blockIdx.x >> 3;
     const uint32_t s = (blockIdx.x & 7u) + 8u * (k / chunks), base = (k % chunks) * kPlaceChunk;
     if (s >= B.nstreams || (B.flags[s] & kFlagHost)) return;
     const uint32_t n = B.n[s], ns = B.nsub[s], mode = B.bwt_mode[s];
     if (base >= n) return;
-    const bool rev = mode == kModeSortA;
-    if (t < 64) {
-        uint32_t nin;
-        make_u2s(B, s, u2s, t, &nin);
-    }
-    {
-        const uint32_t* it = B.itab + (size_t)s * 1024;
-        const uint32_t u = rev ? 255u - t : t;
-        tq[t] = it[t];
-        cs[t] = it[256 + t];
-        cl[t] = it[512 + t];
-        s0[t] = it[768 + t];
-        // (an empty sorted part: never used)
-        cb[t] = it[256 + u] + it[512 + u] + (rev ? B.abcnt[(size_t)s * 512 + t] - 1u : 0u);
-    }
+    place_tabs_load(B, s, mode, P, t);
+    cs[t] = B.itab[(size_t)s * 1024 + 256 + t];
+    cl[t] = B.itab[(size_t)s * 1024 + 512 + t];
     __syncthreads();
     const size_t o = (size_t)s * B.cap;
     const uint8_t* T = B.T + o;
@@ -1867,9 +1989,8 @@ __global__ __launch_bounds__(256) void bwt_place_sorted(Batch B, uint32_t chunks
 #pragma unroll
     for (int q = 0; q < K; ++q) v[q] = B.sa[o + min(base + q * 256 + t, ns ? ns - 1 : 0u)];
 #pragma unroll
-    for (int q = 0; q < K; ++q) {  // two aligned dwords (clamped; the first four rotations wrap)
-        const uint32_t i = v[q] & kIdxMask, a = i >= 4 ? i - 4 : 0u;
-        const uint32_t* w = (const uint32_t*)(T + (a & ~3u));
+    for (int q = 0; q < K; ++q) {
+        const uint32_t* w = place_text_at(T, v[q] & kIdxMask);
         w0[q] = w[0];
         w1[q] = w[1];
     }
@@ -1877,27 +1998,9 @@ __global__ __launch_bounds__(256) void bwt_place_sorted(Batch B, uint32_t chunks
     for (int q = 0; q < K; ++q) {
         const uint32_t j = base + q * 256 + t;
         if (j >= ns) break;
-        const uint32_t i = v[q] & kIdxMask;
-        uint32_t x;  // T[i-4] | T[i-3] << 8 | T[i-2] << 16 | T[i-1] << 24
-        uint32_t c;  // T[i]
-        if (i >= 4) {
-            const uint32_t sh = ((i - 4) & 3u) * 8u;
-            const uint64_t d = (uint64_t)w0[q] | ((uint64_t)w1[q] << 32);
-            x = (uint32_t)(d >> sh);
-            c = (uint32_t)(d >> (sh + 32)) & 0xFFu;
-        } else {
-            x = 0;
-            for (uint32_t r = 1; r <= 4; ++r) x |= (uint32_t)T[(i + 4 * n - r) % n] << (32 - 8 * r);
-            c = T[i];
-        }
-        // its final position is known: the symbol, and origPtr at rotation 0
-        const uint32_t r = j - s0[c], qq = tq[c] + r;
-        LL[qq] = u2s[v[q] >> 24];
-        if (i == 0) B.orig_ptr[s] = qq;
-        if (mode != kModeFull)
-            E[rev ? cb[c] - r : cb[c] + r] =
-                make_uint2(v[q] | (3u << 20),
-                           ((x >> 16) & 0xFFu) | (((x >> 8) & 0xFFu) << 8) | ((x & 0xFFu) << 16) | (c << 24));
+        uint32_t x, c;
+        place_text(T, n, v[q] & kIdxMask, w0[q], w1[q], x, c);
+        place_slot(P, mode, j, v[q], x, c, LL, E, B.orig_ptr + s);
     }
     if (mode == kModeFull) return;
     // the live slots among the compact indices [base, base + kPlaceChunk): of
@@ -1912,6 +2015,46 @@ __global__ __launch_bounds__(256) void bwt_place_sorted(Batch B, uint32_t chunks
     }
     for (uint32_t u = lo; u < 256 && cs[u] < end; ++u)
         for (uint32_t q = max(cs[u], base) + t; q < min(cs[u] + cl[u], end); q += 256) E[q] = make_uint2(kIndPend, 0u);
+}
+
+// The fused path's two small kernels.  bwt_pend_live: kIndPend into a
+// stream's live slots (one workgroup per stream, a wave per scan bucket);
+// they and the sorted slots are disjoint compact indices, so its order against
+// the sorts does not matter.  bwt_place_tied: the slots of the tied list placed
+// again from sa, after tie_runs_direct: a run keeps its slots and positions,
+// only which rotation sits in each changes, so overwriting is enough.
+__global__ __launch_bounds__(256) void bwt_pend_live(Batch B)
+{
+    const uint32_t s = blockIdx.x, lane = threadIdx.x & 63;
+    if (B.flags[s] & kFlagHost) return;
+    const uint32_t n = B.n[s];
+    if (n == 0 || B.bwt_mode[s] == kModeFull) return;
+    __shared__ uint32_t c0[256], c1[256];
+    const uint32_t* it = B.itab + (size_t)s * 1024;
+    uint2* E = B.ent + (size_t)s * B.cap;
+    c0[threadIdx.x] = it[256 + threadIdx.x];
+    c1[threadIdx.x] = min(it[256 + threadIdx.x] + it[512 + threadIdx.x], n);  // (every live range lies below the compact length <= n)
+    __syncthreads();
+    for (uint32_t u = threadIdx.x >> 6; u < 256; u += 4)
+        for (uint32_t q = c0[u] + lane; q < c1[u]; q += 64) E[q] = make_uint2(kIndPend, 0u);
+}
+
+__global__ __launch_bounds__(256) void bwt_place_tied(Batch B, const uint32_t* __restrict__ cl,
+                                                      const uint32_t* __restrict__ cnt_p)
+{
+    const uint32_t cnt = *cnt_p;
+    for (uint32_t c = blockIdx.x * blockDim.x + threadIdx.x; c < cnt; c += gridDim.x * blockDim.x) {
+        const uint32_t slot = cl[c];
+        const uint32_t s = slot / B.cap, n = B.n[s], mode = B.bwt_mode[s];
+        const size_t o = (size_t)s * B.cap;
+        const uint8_t* T = B.T + o;
+        const uint32_t v = B.sa[slot], i = v & kIdxMask;
+        const uint32_t* w = place_text_at(T, i);
+        uint32_t x, ch;
+        place_text(T, n, i, w[0], w[1], x, ch);
+        const PlaceTabsGlobal P{B.itab + (size_t)s * 1024, B.abcnt + (size_t)s * 512, B.inuse + s * 8, mode == kModeSortA};
+        place_slot(P, mode, slot - (uint32_t)o, v, x, ch, (uint8_t*)B.mtfv + o, B.ent + o, B.orig_ptr + s);
+    }
 }
 
 // bwt_induce: one wave per stream scans the compact index, in blocks of
@@ -1960,7 +2103,7 @@ __global__ __launch_bounds__(64) void bwt_induce(Batch B)
     if (B.flags[s] & kFlagHost) return;
     const uint32_t n = B.n[s];
     const uint32_t mode = B.bwt_mode[s];
-    if (n == 0 || mode == kModeFull) return;  // kModeFull: bwt_place_sorted wrote the final order
+    if (n == 0 || mode == kModeFull) return;  // kModeFull: the placement wrote the final order
     const bool rev = mode == kModeSortA;      // right to left, mirrored bytes
     const uint32_t mir = rev ? 255u : 0u;
     const size_t o = (size_t)s * B.cap;
@@ -3885,6 +4028,7 @@ thread_local StageEvents t_stage;
 thread_local void (*t_hook)(void*, int) = nullptr;
 thread_local void* t_hook_ctx = nullptr;
 thread_local uint64_t t_last_blocks = 0;  // bzip2 blocks the calling thread's last call produced (lfm_hip_bzip2_last_blocks)
+thread_local uint32_t t_last_place = 0;  // how its sorted rotations were placed (lfm_hip_bzip2_last_place_path)
 thread_local uint32_t t_last_bwt[12] = {};  // the path its BWT took (lfm_hip_bzip2_last_bwt_stats)
 
 // rocPRIM temporary storage for the largest use of each primitive in a batch
@@ -3947,6 +4091,17 @@ struct BwtStats {
     uint32_t rank_form = 0;       // rank_rebuild: 0 not run, 1 bwt_rank0, 2 from the gathered group keys
     uint32_t doubling_rounds = 0;
     uint32_t flag_periodic = 0;   // bwt_flag_periodic ran
+    bool fused_sorts = false;     // the last attempt's chunk sorts placed their rotations (not part of the report above)
+
+    // How the sorted rotations get placed (lfm_hip_bzip2_last_place_path):
+    // 0 not at all (restarted: mtf_last reads sa), 1 by the chunk sorts and
+    // bwt_place_tied, 2 by bwt_place_sorted over the whole batch -- when the
+    // sorts did not place (segmented chunks), or a run was left to the text
+    // rounds, whose scratch is where the sorts had placed.
+    uint32_t place_path(bool it_full) const
+    {
+        return it_full ? 0u : (fused_sorts && left_runs == 0 && text_rounds == 0) ? 1u : 2u;
+    }
 };
 
 // The workspace, described once: every buffer in order, 256-byte aligned.
@@ -4060,10 +4215,12 @@ uint32_t list_grid(uint32_t cnt) { return std::min<uint32_t>(4096, (cnt + 255) /
 
 // the nc chunks of class `cls`, in XCD-aware order: workgroup b runs on XCD b % 8
 template <int TH, int IPT>
-void chunk_sorts(const Batch& B, const ChunkLists& CL, int cls, uint32_t nc, hipStream_t st)
+void chunk_sorts(const Batch& B, const ChunkLists& CL, int cls, uint32_t nc, bool place, hipStream_t st)
 {
     const uint32_t per = (nc + 7) / 8;
-    if (nc) hipLaunchKernelGGL((bwt_chunk_sort<TH, IPT>), dim3(8 * per), dim3(TH), 0, st, B, CL.b[cls], CL.e[cls], nc, per);
+    if (!nc) return;
+    if (place) hipLaunchKernelGGL((bwt_chunk_sort<TH, IPT, true>), dim3(8 * per), dim3(TH), 0, st, B, CL.b[cls], CL.e[cls], nc, per);
+    else hipLaunchKernelGGL((bwt_chunk_sort<TH, IPT, false>), dim3(8 * per), dim3(TH), 0, st, B, CL.b[cls], CL.e[cls], nc, per);
 }
 
 // Round 0: the bucket pass, the chunk sorts by the 8-byte prefix (one host
@@ -4093,9 +4250,18 @@ hipError_t first_round(const Batch& B, TieRounds& W)
     W.stats.chunks[2] = nch[1];
     W.stats.chunks[3] = nch[2];
     W.stats.first_ties = W.stats.left_runs = W.stats.text_rounds = 0;
-    chunk_sorts<kTinyCap / kCsItems, kCsItems>(B, CL, 3, nch[5], st);
-    chunk_sorts<kCsThreads, kCsItems>(B, CL, 0, nch[0], st);
-    chunk_sorts<kBigThreads, kBigItems>(B, CL, 1, nch[1], st);
+    // The sorts place their rotations themselves (PLACE) when the batch is
+    // induced and every chunk goes through them: the segmented sort's keys
+    // lie in keys_a, where the entries go.  Between the sorts and bwt_induce
+    // only tie_offsets (done), tie_compact (cl0), tie_runs_direct (sa, cnt[7])
+    // and the two small kernels below run on that path, and none of them
+    // writes keys_a or mtfv (the symbols); a text round would (its scratch is
+    // both), which is why a call that runs one places the whole batch again.
+    const bool fused = !B.it_full && nch[2] == 0;
+    W.stats.fused_sorts = fused;
+    chunk_sorts<kTinyCap / kCsItems, kCsItems>(B, CL, 3, nch[5], fused, st);
+    chunk_sorts<kCsThreads, kCsItems>(B, CL, 0, nch[0], fused, st);
+    chunk_sorts<kBigThreads, kBigItems>(B, CL, 1, nch[1], fused, st);
     if (nch[2]) {
         hipLaunchKernelGGL(bwt_chunk_keys, dim3(nch[2]), dim3(256), 0, st, B, CL.b[2], CL.e[2]);
         e = rocprim::segmented_radix_sort_pairs(W.tmp, W.tmp_bytes, B.keys_a, B.keys_b, B.vals_a, B.sa,
@@ -4109,6 +4275,10 @@ hipError_t first_round(const Batch& B, TieRounds& W)
     hipLaunchKernelGGL(tie_offsets, dim3(1), dim3(1024), 0, st, B, W.cnt);
     hipLaunchKernelGGL(tie_compact, dim3(count), dim3(256), 0, st, B, B.cl0);
     hipLaunchKernelGGL(tie_runs_direct, dim3(1024), dim3(256), 0, st, B, B.cl0, W.cnt, W.cnt + 7);
+    if (fused) {  // queued ahead of the host's read of the counts; void if a run was left (place_path)
+        hipLaunchKernelGGL(bwt_place_tied, dim3(256), dim3(256), 0, st, B, B.cl0, W.cnt);
+        hipLaunchKernelGGL(bwt_pend_live, dim3(count), dim3(256), 0, st, B);
+    }
     W.covered = kKeyBytes;
     W.none_left = false;
     return hipGetLastError();
@@ -4350,7 +4520,9 @@ int bzip2_blocks(const void* d_img, const uint32_t dims[5], const uint32_t bs[5]
     // BWT: the rotations of one type sorted (bwt_sort), every other rotation
     // placed by bwt_induce unless bwt_sort had to sort them all (B.it_full)
     BwtStats bwt_stats;
+    B.ent = (uint2*)B.keys_a;  // (free after the sorts; the chunk sorts themselves write it when they place)
     if (bwt_sort(B, S, st, &bwt_stats) != hipSuccess) return LFM_HIP_ERUNTIME;
+    t_last_place = bwt_stats.place_path(B.it_full != 0);
     {
         const uint32_t v[12] = {bwt_stats.chunks[0], bwt_stats.chunks[1], bwt_stats.chunks[2], bwt_stats.chunks[3],
                                 bwt_stats.first_ties, bwt_stats.left_runs, bwt_stats.text_rounds, bwt_stats.restarted,
@@ -4359,9 +4531,9 @@ int bzip2_blocks(const void* d_img, const uint32_t dims[5], const uint32_t bs[5]
     }
     if (!B.it_full) {
         // the other type placed by one scan, which writes the symbols ll[]
-        B.ent = (uint2*)B.keys_a;
         const uint32_t chunks = (B.cap + kPlaceChunk - 1) / kPlaceChunk;
-        hipLaunchKernelGGL(bwt_place_sorted, dim3(8 * chunks * ((count + 7) / 8)), dim3(256), 0, st, B, chunks);
+        if (t_last_place == 2)
+            hipLaunchKernelGGL(bwt_place_sorted, dim3(8 * chunks * ((count + 7) / 8)), dim3(256), 0, st, B, chunks);
         hipLaunchKernelGGL(bwt_induce, dim3(count), dim3(64), 0, st, B);
         if (!ok()) return LFM_HIP_ERUNTIME;
     }
@@ -4489,6 +4661,8 @@ extern "C" void lfm_hip_bzip2_last_bwt_stats(uint32_t out[12])
 {
     if (out) std::copy(t_last_bwt, t_last_bwt + 12, out);
 }
+
+extern "C" uint32_t lfm_hip_bzip2_last_place_path(void) { return t_last_place; }
 
 extern "C" int lfm_hip_bzip2_last_stage_ms(float ms[5])
 {

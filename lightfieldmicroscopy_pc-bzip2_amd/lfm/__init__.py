@@ -51,6 +51,7 @@ EXPORTS = [
     "lfm_hip_bzip2_blocks", "lfm_hip_bzip2_last_stage_ms", "lfm_hip_bunzip2_workspace_bytes", "lfm_hip_bunzip2_blocks", "lfm_hip_scatter_blocks",
     "lfm_hip_crop_region", "lfm_hip_bzip2_workspace_bytes_multi", "lfm_hip_bzip2_max_count_multi",
     "lfm_hip_bzip2_blocks_multi", "lfm_hip_bzip2_last_blocks", "lfm_hip_bzip2_last_bwt_stats",
+    "lfm_hip_bzip2_last_place_path",
     "lfm_hip_bunzip2_max_parts", "lfm_hip_bunzip2_workspace_bytes_multi", "lfm_hip_bunzip2_blocks_multi",
     "lfm_hip_bunzip2_issue_multi", "lfm_hip_bunzip2_set_periodic", "lfm_hip_bunzip2_get_periodic",
 ]
@@ -192,6 +193,8 @@ def lib():
     L.lfm_hip_bzip2_last_blocks.restype = ctypes.c_uint64
     L.lfm_hip_bzip2_last_bwt_stats.argtypes = [u32p]
     L.lfm_hip_bzip2_last_bwt_stats.restype = None
+    L.lfm_hip_bzip2_last_place_path.argtypes = []
+    L.lfm_hip_bzip2_last_place_path.restype = ctypes.c_uint32
     L.lfm_set_bzip2_multiblock.argtypes = [ctypes.c_int]
     L.lfm_get_bzip2_multiblock.argtypes = []
     L.lfm_encoder_stream_counts.argtypes = [vp] + [ctypes.POINTER(ctypes.c_uint64)] * 3
@@ -987,6 +990,13 @@ def bzip2_last_bwt_stats():
     out = (ctypes.c_uint32 * 12)()
     lib().lfm_hip_bzip2_last_bwt_stats(out)
     return dict(zip(BWT_STATS, list(out)))
+
+
+def bzip2_last_place_path():
+    """How the sorted rotations of this thread's last bzip2_device call were
+    placed (lfm_hip_bzip2_last_place_path, lfm_hip.h): 0 not at all (restart),
+    1 by the chunk sorts, 2 by the placement kernel over the whole batch."""
+    return int(lib().lfm_hip_bzip2_last_place_path())
 
 
 def set_bunzip2_multiblock(on):
