@@ -9,6 +9,9 @@
  *    ctypes / cgo / JNI callers (matlabWrapper/writeLFMstack.cpp:360-433).
  *  - lfm_encoder_*: reusable encoder context that encodes to memory from a
  *    host or a DEVICE-resident stack and reports per-stage timings (bench).
+ *  - lfm_writer_* / lfm_reader_*: stacks larger than memory -- block layers
+ *    appended over time to one .lfm file, and region reads that fetch only
+ *    the bytes of the blocks they need (at the end of this file).
  */
 #ifndef LFM_API_H
 #define LFM_API_H
@@ -334,6 +337,94 @@ LFM_API int lfm_decode_memory_multi(const uint8_t* buf, uint64_t len, void* img,
 LFM_API int lfm_decode_memory_multi_device(const uint8_t* buf, uint64_t len, void* const* d_out,
                                            const uint64_t* out_bytes, int nshards, int numThreads,
                                            lfm_decode_multi_stats* stats, lfm_decode_shard* shards, int shard_cap);
+
+/* ---- stream writer: one .lfm file from block layers that arrive over time ----
+ * The stream axis is the writers' shard axis: t when xyzct[4] > 1, else c
+ * when xyzct[3] > 1, else z (lfm_writer_axis: 4, 3 or 2).  xyzct[axis] at open
+ * is the CAPACITY: the most indices that may be appended.  The other
+ * arguments are lfm_encoder_encode's (headerVersion = predictor request |
+ * video << 7) and writeLFMstack_c's (pixelSize, metadata; NULL = defaults).
+ *
+ * lfm_writer_append takes count >= 1 consecutive indices along the axis (host
+ * memory, or device memory on the writer's device; x fastest; any count).
+ * The writer encodes whole block layers, blockSize[axis] indices each, on an
+ * encoder of its own on `device` (< 0: the current one), pipelined like
+ * lfm_encoder_submit, two encodes in flight; every full layer one append
+ * completes goes into one encode.  Fewer than one layer is held back, in
+ * memory of the input's kind (stats.staged_peak_bytes); an append that starts
+ * and ends on a layer boundary is encoded from the caller's memory without a
+ * copy.  When append returns, the library has finished reading img; the
+ * compressed bytes may reach the file later, and an error of a background
+ * encode is returned by the next append or by close.  A device input is read
+ * after the work queued on the device's null stream, as lfm_encoder_submit
+ * reads its input.  The predictor is selected once, on frame 0 of the first
+ * append, and forced for every encode; the bzip2 level is the level of the
+ * stack's nominal block.  Returns 3 and takes nothing: count 0, an append
+ * past the capacity, host and device appends mixed in one writer.  After any
+ * other non-zero return the writer is failed: every later call returns that
+ * code and close removes the file.
+ *
+ * File: the fixed header and a zero offset table sized for the capacity are
+ * written at open, the payload follows in block order, and close writes the
+ * table and the final xyzct[axis].  When fewer indices than the capacity were
+ * appended the final table is shorter by 8 * (Nb_capacity - Nb_final) bytes:
+ * close moves the payload down by that much (a forward chunked copy,
+ * stats.moved_bytes) and truncates the file.  After close the file is
+ * byte-identical to what writeLFMstack_c / lfm_encoder_encode produce for the
+ * appended stack with the same arguments and xyzct[axis] = what was appended
+ * (a final extent below blockSize[axis] included: that single layer is
+ * encoded at close, with the block and the bzip2 level the one-shot writer
+ * would clamp to).  A file that was never closed has a zero table and is NOT
+ * a valid .lfm; there is no recovery of one.
+ * lfm_writer_close finalises and frees the writer whatever it returns; a
+ * close with nothing appended returns 3 and removes the file.
+ * lfm_writer_abort frees the writer and removes the file.  One writer is
+ * used by one thread at a time. */
+typedef struct lfm_writer lfm_writer;
+typedef struct lfm_writer_stats {
+    uint64_t appended;       /* indices along the stream axis taken so far            */
+    uint64_t ranges;         /* encodes run                                           */
+    uint64_t streams, host_streams, bzip2_blocks;   /* summed over the ranges         */
+    uint64_t bytes_written;  /* final file size (after close)                         */
+    uint64_t moved_bytes;    /* payload bytes moved at close (0 when capacity reached) */
+    uint64_t staged_peak_bytes; /* most input bytes the writer held back at one time  */
+    int chosen, header_version; float entropy[8];
+    double total_ms;         /* wall clock spent inside append and close              */
+} lfm_writer_stats;
+
+LFM_API int lfm_writer_open(lfm_writer** w, const char* filename, const uint32_t xyzct[KLB_DATA_DIMS], int dataType,
+                            int headerVersion, int Nnum, const float pixelSize[KLB_DATA_DIMS],
+                            const uint32_t blockSize[KLB_DATA_DIMS], int compressionType,
+                            const char metadata[KLB_METADATA_SIZE], int device, int numThreads);
+LFM_API int lfm_writer_axis(const lfm_writer* w);   /* 4, 3 or 2 */
+LFM_API int lfm_writer_append(lfm_writer* w, const void* img, int img_is_device, uint32_t count);
+LFM_API int lfm_writer_close(lfm_writer* w, lfm_writer_stats* stats);   /* finalises and frees */
+LFM_API void lfm_writer_abort(lfm_writer* w);                           /* frees, removes the file */
+
+/* ---- ranged reader: region reads that fetch only the bytes they need ----
+ * lfm_reader_open reads the fixed header and the offset table, nothing else
+ * (2: the file cannot be opened, is truncated, or its table points past its
+ * end -- a file its writer never closed).  lfm_reader_read decodes the region
+ * lb .. ub (inclusive, xyzct) as lfm_decode_memory_roi (out_is_device == 0)
+ * or lfm_decode_memory_roi_device (!= 0) do -- the same blocks, return codes,
+ * device ordering and lfm_decode_stats (stats may be NULL) -- but the streams
+ * of those blocks are read from the file: one pread per run of blocks that
+ * lie one after the other in it, no byte between the runs.  The blocks are
+ * the ones the region depends on: with a predictor the corner up and left of
+ * the region in its frames, plus the frame before an odd z of a video stack.
+ * A region equal to the whole image is allowed.  lfm_reader_bytes_read is the
+ * cumulative count of bytes read from the file, header and table included.
+ * One reader is used by one thread at a time. */
+typedef struct lfm_reader lfm_reader;
+LFM_API int lfm_reader_open(lfm_reader** r, const char* filename);        /* header + table only */
+LFM_API int lfm_reader_info(const lfm_reader* r, uint32_t xyzct[KLB_DATA_DIMS], int* dataType,
+                            uint32_t blockSize[KLB_DATA_DIMS], uint8_t* headerVersion, uint8_t* Nnum,
+                            uint64_t* file_bytes);
+LFM_API int lfm_reader_read(lfm_reader* r, const uint32_t lb[KLB_DATA_DIMS], const uint32_t ub[KLB_DATA_DIMS],
+                            void* out, uint64_t out_bytes, int out_is_device, int numThreads,
+                            lfm_decode_stats* stats);
+LFM_API uint64_t lfm_reader_bytes_read(const lfm_reader* r);              /* cumulative, header + table included */
+LFM_API void lfm_reader_close(lfm_reader* r);
 
 #ifdef __cplusplus
 }

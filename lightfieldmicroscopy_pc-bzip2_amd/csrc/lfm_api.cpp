@@ -348,6 +348,98 @@ extern "C" int lfm_decode_memory_roi_device(const uint8_t* buf, uint64_t len, co
     return lfm::decode_memory_device(buf, len, lb, ub, d_out, out_bytes, numThreads, stats);
 }
 
+// ---- stream writer / ranged reader (lfm_stream.cpp) ----
+struct lfm_writer {
+    lfm::StreamWriter w;
+    lfm_writer(const klb_image_header& h, int device, int threads) : w(h, device, threads) {}
+};
+struct lfm_reader {
+    lfm::FileReader r;
+};
+
+extern "C" int lfm_writer_open(lfm_writer** w, const char* filename, const uint32_t xyzct[KLB_DATA_DIMS], int dataType,
+                               int headerVersion, int Nnum, const float pixelSize[KLB_DATA_DIMS],
+                               const uint32_t blockSize[KLB_DATA_DIMS], int compressionType,
+                               const char metadata[KLB_METADATA_SIZE], int device, int numThreads)
+{
+    if (!w) return 3;
+    *w = nullptr;
+    if (!filename || !xyzct) return 3;
+    klb_image_header h;
+    h.setHeader(xyzct, (KLB_DATA_TYPE)dataType, pixelSize, blockSize, (KLB_COMPRESSION_TYPE)compressionType, metadata,
+                (uint8_t)headerVersion, (uint8_t)Nnum);
+    lfm_writer* p = new lfm_writer(h, device, numThreads);
+    if (int rc = p->w.open(filename)) {
+        p->w.abort();
+        delete p;
+        return rc;
+    }
+    *w = p;
+    return 0;
+}
+
+extern "C" int lfm_writer_axis(const lfm_writer* w) { return w ? w->w.axis() : -1; }
+
+extern "C" int lfm_writer_append(lfm_writer* w, const void* img, int img_is_device, uint32_t count)
+{
+    return w ? w->w.append(img, img_is_device != 0, count) : 3;
+}
+
+extern "C" int lfm_writer_close(lfm_writer* w, lfm_writer_stats* stats)
+{
+    if (!w) return 3;
+    const int rc = w->w.close(stats);
+    delete w;
+    return rc;
+}
+
+extern "C" void lfm_writer_abort(lfm_writer* w)
+{
+    if (!w) return;
+    w->w.abort();
+    delete w;
+}
+
+extern "C" int lfm_reader_open(lfm_reader** r, const char* filename)
+{
+    if (!r) return 3;
+    *r = nullptr;
+    if (!filename) return 3;
+    lfm_reader* p = new lfm_reader;
+    if (int rc = p->r.open(filename)) {
+        delete p;
+        return rc;
+    }
+    *r = p;
+    return 0;
+}
+
+extern "C" int lfm_reader_info(const lfm_reader* r, uint32_t xyzct[KLB_DATA_DIMS], int* dataType,
+                               uint32_t blockSize[KLB_DATA_DIMS], uint8_t* headerVersion, uint8_t* Nnum,
+                               uint64_t* file_bytes)
+{
+    if (!r) return 3;
+    const klb_image_header& h = r->r.h;
+    if (xyzct) std::memcpy(xyzct, h.xyzct, sizeof(h.xyzct));
+    if (dataType) *dataType = (int)h.dataType;
+    if (blockSize) std::memcpy(blockSize, h.blockSize, sizeof(h.blockSize));
+    if (headerVersion) *headerVersion = h.headerVersion;
+    if (Nnum) *Nnum = h.Nnum;
+    if (file_bytes) *file_bytes = r->r.file_bytes;
+    return 0;
+}
+
+extern "C" int lfm_reader_read(lfm_reader* r, const uint32_t lb[KLB_DATA_DIMS], const uint32_t ub[KLB_DATA_DIMS],
+                               void* out, uint64_t out_bytes, int out_is_device, int numThreads,
+                               lfm_decode_stats* stats)
+{
+    return r ? r->r.read(lb, ub, out, out_bytes, out_is_device != 0, numThreads, stats) : 3;
+}
+
+extern "C" uint64_t lfm_reader_bytes_read(const lfm_reader* r) { return r ? r->r.bytes_read : 0; }
+
+extern "C" void lfm_reader_close(lfm_reader* r) { delete r; }
+
 extern "C" int lfm_decode_memory_roi(const uint8_t* buf, uint64_t len, const uint32_t lb[KLB_DATA_DIMS],
                                      const uint32_t ub[KLB_DATA_DIMS], void* out, uint64_t out_bytes, int numThreads)
 {

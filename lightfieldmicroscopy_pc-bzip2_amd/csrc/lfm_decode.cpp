@@ -806,6 +806,18 @@ int decode_payload(const uint8_t* payload, size_t len, const klb_image_header& h
 int decode_roi(const uint8_t* payload, size_t len, const klb_image_header& h, const uint32_t lb[5],
                const uint32_t ub[5], uint8_t* out, int threads, int family, DeviceDest* dd, lfm_decode_stats* hstats)
 {
+    PayloadSource src;
+    src.mem = payload;
+    src.len = len;
+    return decode_roi(src, h, lb, ub, out, threads, family, dd, hstats);
+}
+
+int decode_roi(const PayloadSource& src, const klb_image_header& h, const uint32_t lb[5], const uint32_t ub[5],
+               uint8_t* out, int threads, int family, DeviceDest* dd, lfm_decode_stats* hstats)
+{
+    const uint8_t* const payload = src.mem;
+    const uint64_t len = src.len;
+    if (!payload && src.fd < 0) return 3;
     const BlockGrid g(h);
     if (g.nblocks != h.Nb) return 3;
     const size_t bpp = h.getBytesPerPixel();
@@ -856,8 +868,29 @@ int decode_roi(const uint8_t* payload, size_t len, const klb_image_header& h, co
         run = ids[i] == ids[i - 1] + 1 && h.getBlockOffset(ids[i]) == h.getBlockOffset(ids[i - 1]) +
                                                                          h.getBlockCompressedSizeBytes(ids[i - 1]);
     std::unique_ptr<uint8_t[]> gathered;
-    const uint8_t* spay = ids.empty() ? payload : payload + h.getBlockOffset(ids[0]);
-    if (!run) {
+    const uint8_t* spay = (ids.empty() || !payload) ? payload : payload + h.getBlockOffset(ids[0]);
+    if (!payload) {
+        // the payload is a file: each run of blocks that lie one after the
+        // other in it is fetched with one read into its place in the
+        // sub-payload; the bytes between the runs are never read
+        struct Run {
+            uint64_t from, to, bytes;  // file offset, sub-payload offset
+        };
+        std::vector<Run> runs;
+        for (size_t i = 0; i < ids.size(); ++i) {
+            const uint64_t off = h.getBlockOffset(ids[i]), sz = h.getBlockCompressedSizeBytes(ids[i]);
+            if (!runs.empty() && runs.back().from + runs.back().bytes == off) runs.back().bytes += sz;
+            else runs.push_back(Run{off, sub.blockOffset[i] - sz, sz});
+        }
+        gathered.reset(new uint8_t[total ? total : 1]);
+        std::atomic<bool> bad{false};
+        parallel_for(runs.size(), threads, [&](uint64_t r) {
+            if (!pread_all(src.fd, gathered.get() + runs[r].to, runs[r].bytes, src.base + runs[r].from)) bad.store(true);
+        });
+        if (bad.load()) return 3;
+        if (src.fetched) *src.fetched += total;
+        spay = gathered.get();
+    } else if (!run) {
         gathered.reset(new uint8_t[total]);
         parallel_for(ids.size(), threads, [&](uint64_t i) {
             const uint64_t id = ids[i], sz = h.getBlockCompressedSizeBytes(id);
@@ -917,11 +950,23 @@ int decode_roi(const uint8_t* payload, size_t len, const klb_image_header& h, co
 int decode_memory_device(const uint8_t* buf, uint64_t len, const uint32_t* lb, const uint32_t* ub, void* d_out,
                          uint64_t out_bytes, int threads, lfm_decode_stats* stats)
 {
-    const auto t0 = std::chrono::steady_clock::now();
     if (!buf || !d_out || (lb == nullptr) != (ub == nullptr)) return 3;
     klb_image_header h;
     int rc = h.parseHeader(buf, len);
     if (rc) return rc;
+    const size_t hs = h.getSizeInBytes();
+    PayloadSource src;
+    src.mem = buf + hs;
+    src.len = len - hs;
+    return decode_source_device(src, h, lb, ub, d_out, out_bytes, threads, stats);
+}
+
+int decode_source_device(const PayloadSource& src, const klb_image_header& h, const uint32_t* lb, const uint32_t* ub,
+                         void* d_out, uint64_t out_bytes, int threads, lfm_decode_stats* stats)
+{
+    const auto t0 = std::chrono::steady_clock::now();
+    if (!d_out || (lb == nullptr) != (ub == nullptr) || (!src.mem && (src.fd < 0 || !lb))) return 3;
+    int rc = 0;
     uint64_t need = h.getImageSizeBytes();
     if (lb) {
         need = h.getBytesPerPixel();  // the region in the file's own data type
@@ -946,10 +991,9 @@ int decode_memory_device(const uint8_t* buf, uint64_t len, const uint32_t* lb, c
     if (hipEventCreateWithFlags(&dd.after_caller, hipEventDisableTiming) != hipSuccess ||
         hipEventRecord(dd.after_caller, nullptr) != hipSuccess)
         rc = 3;
-    const size_t hs = h.getSizeInBytes();
     if (!rc)
-        rc = lb ? decode_roi(buf + hs, len - hs, h, lb, ub, (uint8_t*)d_out, threads, current_family(), &dd)
-                : decode_payload(buf + hs, len - hs, h, (uint8_t*)d_out, threads, current_family(), &dd);
+        rc = lb ? decode_roi(src, h, lb, ub, (uint8_t*)d_out, threads, current_family(), &dd)
+                : decode_payload(src.mem, src.len, h, (uint8_t*)d_out, threads, current_family(), &dd);
     if (dd.after_caller) (void)hipEventDestroy(dd.after_caller);
     if (attr.device != cur) (void)hipSetDevice(cur);
     dd.stats.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();

@@ -1006,6 +1006,13 @@ int Encoder::preselect(const void* img, bool dev, const klb_image_header& h, con
                : 3;
 }
 
+int Encoder::select_frame(const void* frame, bool dev, const klb_image_header& h, int* chosen, float entropy[8])
+{
+    static const SlabSpec whole;
+    if (int rc = after_caller(dev)) return rc;
+    return preselect(frame, dev, h, whole, chosen, entropy);
+}
+
 int Encoder::select_host_frame(const void* frame, int W, int H, int T, int family, int* chosen, float entropy[8])
 {
     if (int rc = ensure_gpu()) return rc;

@@ -7,6 +7,7 @@
 #include <cstdio>
 #include <memory>
 #include <mutex>
+#include <string>
 #include <thread>
 #include <vector>
 #include <hip/hip_runtime.h>
@@ -187,6 +188,10 @@ public:
     StreamCounts last_counts;
     // predictor selection on one host frame (uploaded to this encoder's device)
     int select_host_frame(const void* frame, int W, int H, int T, int family, int* chosen, float entropy[8]);
+    // predictor selection on one frame of h's x / y size, host or device
+    // (a device frame is read after the null stream's queued work, as submit
+    // reads its input): the stream writer selects once, on its first frame
+    int select_frame(const void* frame, bool dev, const klb_image_header& h, int* chosen, float entropy[8]);
 
 private:
     // an encode in flight (submit): its finisher thread and the release point
@@ -337,11 +342,28 @@ int decode_file(const char* filename, klb_image_header& h, std::vector<uint8_t>*
 int decode_roi(const uint8_t* payload, size_t len, const klb_image_header& h, const uint32_t lb[5],
                const uint32_t ub[5], uint8_t* out, int threads, int family, DeviceDest* dd = nullptr,
                lfm_decode_stats* hstats = nullptr);
+// Where a region read takes the streams of its blocks from: the payload in
+// memory (`mem`, the bytes after the header), or a file it is fetched from by
+// byte range (`fd`, the payload starting at file offset `base`): one pread per
+// run of blocks that lie one after the other, nothing between the runs.  The
+// block list, the sub-header and the decode are the same for both.
+struct PayloadSource {
+    const uint8_t* mem = nullptr;
+    int fd = -1;
+    uint64_t base = 0;
+    uint64_t len = 0;              // payload bytes
+    uint64_t* fetched = nullptr;   // file source: the bytes read are added here
+};
+int decode_roi(const PayloadSource& src, const klb_image_header& h, const uint32_t lb[5], const uint32_t ub[5],
+               uint8_t* out, int threads, int family, DeviceDest* dd = nullptr, lfm_decode_stats* hstats = nullptr);
 // The two device-destination readers behind the C ABI: find the buffer's
 // device (3 for a host or unregistered pointer), run the decode there with the
 // ordering of DeviceDest and restore the caller's current device.
 int decode_memory_device(const uint8_t* buf, uint64_t len, const uint32_t* lb, const uint32_t* ub, void* d_out,
                          uint64_t out_bytes, int threads, lfm_decode_stats* stats);
+// the same for a parsed header and a payload source (a file source reads a region: lb / ub given)
+int decode_source_device(const PayloadSource& src, const klb_image_header& h, const uint32_t* lb, const uint32_t* ub,
+                         void* d_out, uint64_t out_bytes, int threads, lfm_decode_stats* stats);
 int decode_file_roi(const char* filename, klb_image_header& h, const uint32_t lb[5], const uint32_t ub[5],
                     uint8_t* out, int threads);
 
@@ -385,5 +407,67 @@ int decode_multi(const uint8_t* buf, size_t len, const klb_image_header& h, uint
 int decode_image(const uint8_t* buf, size_t len, const klb_image_header& h, uint8_t* img, int threads);
 // stop the kept decode workers; their device and pinned buffers are freed
 void release_decode_workers();
+
+// ---- streaming (lfm_stream.cpp) ----
+// lfm_writer: block layers along the shard axis (t, else c, else z) arrive
+// over time and go into one .lfm file.  Each range of whole layers is encoded
+// as encode_multi encodes its ranges (predictor selected once on frame 0 and
+// forced, the stack's nominal bzip2 level, z0 / prev on the z axis) through
+// Encoder::submit / wait on an encoder of its own, two in flight; the calling
+// thread is the in-order writer: a finished range's payload is appended to
+// the file and its block sizes re-accumulated into the offset table, which
+// close writes with the final extent.
+class StreamWriter {
+public:
+    // h: the stack as lfm_writer_open describes it, xyzct[axis] the capacity
+    StreamWriter(const klb_image_header& h, int device, int threads);
+    ~StreamWriter();
+    int open(const char* filename);
+    int axis() const { return axis_; }
+    int append(const void* img, bool dev, uint32_t count);
+    int close(lfm_writer_stats* st);  // the writer is finished either way
+    void abort();                     // closes and removes the file
+
+private:
+    int submit_range(const void* data, bool dev, uint64_t n);
+    int drain_one();
+    int stage_copy(void* dst, const void* src, size_t n, bool dev);
+    void* stage_buffer(bool dev, int which, size_t n);
+    int finish_file();
+    Encoder enc_;
+    klb_image_header cap_;       // block size as asked for, xyzct[axis] the capacity
+    int threads_, axis_;
+    uint64_t unit_, stride_;     // indices per block layer; bytes per index
+    std::string path_;
+    int fd_ = -1;
+    int rc_ = 0;                 // sticky failure
+    int kind_ = -1;              // -1 none yet, 0 host appends, 1 device appends
+    bool selected_ = false;
+    uint8_t hv_;                 // the request every range is encoded with (forced once selected)
+    uint8_t hv_final_ = 0;       // the header byte the ranges produced
+    uint64_t appended_ = 0, submitted_ = 0, staged_ = 0;  // indices: taken, handed to the encoder, held back
+    bool have_prev_ = false;
+    std::vector<uint8_t> h_buf_[3];  // host: held-back part, assembled range, raw frame before the next range
+    DeviceBuffer d_buf_[3];          // device: the same
+    std::vector<uint64_t> pending_;  // tickets in flight, oldest first
+    std::vector<uint64_t> table_;    // block end offsets so far
+    uint64_t payload_ = 0, payload_base_ = 0, nb_cap_ = 0;
+    lfm_writer_stats st_{};
+};
+
+// lfm_reader: header and table in memory, the streams of a region's blocks
+// fetched from the file by byte range (PayloadSource) for each read.
+class FileReader {
+public:
+    ~FileReader();
+    int open(const char* filename);
+    int read(const uint32_t lb[5], const uint32_t ub[5], void* out, uint64_t out_bytes, bool dev, int threads,
+             lfm_decode_stats* stats);
+    klb_image_header h;
+    uint64_t file_bytes = 0, bytes_read = 0;
+
+private:
+    int fd_ = -1;
+};
 
 } // namespace lfm

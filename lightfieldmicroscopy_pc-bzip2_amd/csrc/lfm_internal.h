@@ -1,5 +1,5 @@
 // lfm_internal.h -- what the host engine's files (lfm_engine.cpp,
-// lfm_encode.cpp, lfm_decode.cpp, lfm_decode_multi.cpp, lfm_transfer.cpp) share with each other and
+// lfm_encode.cpp, lfm_decode.cpp, lfm_decode_multi.cpp, lfm_transfer.cpp, lfm_stream.cpp) share with each other and
 // with nobody else.  Nothing here is exported from liblfm.so.
 #pragma once
 #include <algorithm>
@@ -61,6 +61,10 @@ void parallel_for(uint64_t n, int threads, F&& f)
 int compress_one(int ctype, uint8_t* in, uint32_t n, uint8_t* out, uint32_t cap, uint32_t* out_len,
                  int level);
 int decompress_one(int ctype, const uint8_t* in, uint32_t n, uint8_t* out, uint32_t expect);
+
+// every byte of [off, off + n) of an open file read / written, or false (lfm_stream.cpp)
+bool pread_all(int fd, uint8_t* dst, uint64_t n, uint64_t off);
+bool pwrite_all(int fd, const uint8_t* src, uint64_t n, uint64_t off);
 
 } // namespace lfm
 #pragma GCC visibility pop

@@ -43,6 +43,8 @@ EXPORTS = [
     "lfm_set_bzip2_multiblock", "lfm_get_bzip2_multiblock", "lfm_encoder_stream_counts",
     "lfm_set_bunzip2_multiblock", "lfm_get_bunzip2_multiblock",
     "lfm_set_bunzip2_periodic", "lfm_get_bunzip2_periodic",
+    "lfm_writer_open", "lfm_writer_axis", "lfm_writer_append", "lfm_writer_close", "lfm_writer_abort",
+    "lfm_reader_open", "lfm_reader_info", "lfm_reader_read", "lfm_reader_bytes_read", "lfm_reader_close",
     # lfm_hip.h
     "lfm_hip_predict", "lfm_hip_unpredict", "lfm_hip_unpredict_async", "lfm_hip_unpredict_check",
     "lfm_hip_unpredict_path",
@@ -101,6 +103,20 @@ class DecodeMultiStats(ctypes.Structure):
 
     def as_dict(self):
         return {f: getattr(self, f) for f, _ in self._fields_}
+
+
+class WriterStats(ctypes.Structure):
+    """lfm_writer_stats (lfm_api.h)."""
+    _fields_ = [("appended", ctypes.c_uint64), ("ranges", ctypes.c_uint64), ("streams", ctypes.c_uint64),
+                ("host_streams", ctypes.c_uint64), ("bzip2_blocks", ctypes.c_uint64),
+                ("bytes_written", ctypes.c_uint64), ("moved_bytes", ctypes.c_uint64),
+                ("staged_peak_bytes", ctypes.c_uint64), ("chosen", ctypes.c_int), ("header_version", ctypes.c_int),
+                ("entropy", ctypes.c_float * 8), ("total_ms", ctypes.c_double)]
+
+    def as_dict(self):
+        d = {f: getattr(self, f) for f, _ in self._fields_ if f != "entropy"}
+        d["entropy"] = list(self.entropy)
+        return d
 
 
 _lib = None
@@ -254,6 +270,26 @@ def lib():
                                                      ctypes.POINTER(ctypes.c_uint64), ctypes.c_int, ctypes.c_int,
                                                      ctypes.POINTER(DecodeMultiStats), ctypes.POINTER(DecodeShard),
                                                      ctypes.c_int]
+    # the stream writer and the ranged reader, likewise
+    if hasattr(L, "lfm_writer_open"):
+        L.lfm_writer_open.argtypes = [ctypes.POINTER(vp), ctypes.c_char_p, u32p, ctypes.c_int, ctypes.c_int,
+                                      ctypes.c_int, f32p, u32p, ctypes.c_int, ctypes.c_char_p, ctypes.c_int,
+                                      ctypes.c_int]
+        L.lfm_writer_axis.argtypes = [vp]
+        L.lfm_writer_append.argtypes = [vp, vp, ctypes.c_int, ctypes.c_uint32]
+        L.lfm_writer_close.argtypes = [vp, ctypes.POINTER(WriterStats)]
+        L.lfm_writer_abort.argtypes = [vp]
+        L.lfm_writer_abort.restype = None
+    if hasattr(L, "lfm_reader_open"):
+        L.lfm_reader_open.argtypes = [ctypes.POINTER(vp), ctypes.c_char_p]
+        L.lfm_reader_info.argtypes = [vp, u32p, intp, u32p, ctypes.POINTER(ctypes.c_uint8),
+                                      ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(ctypes.c_uint64)]
+        L.lfm_reader_read.argtypes = [vp, u32p, u32p, vp, ctypes.c_uint64, ctypes.c_int, ctypes.c_int,
+                                      ctypes.POINTER(DecodeStats)]
+        L.lfm_reader_bytes_read.argtypes = [vp]
+        L.lfm_reader_bytes_read.restype = ctypes.c_uint64
+        L.lfm_reader_close.argtypes = [vp]
+        L.lfm_reader_close.restype = None
     _lib = L
     return L
 
@@ -735,6 +771,195 @@ def read_lfm_device(path, out=None, device=None, num_threads=-1, return_stats=Fa
     with open(path, "rb") as f:
         buf = f.read()
     return decode_device(buf, out=out, device=device, num_threads=num_threads, return_stats=return_stats)
+
+
+# ------------------------------------------- streaming to and from a file --
+class Writer:
+    """lfm_writer: one .lfm file from block layers appended over time.
+
+    shape: the stack's [t, c, z, y, x] (or fewer leading dims); its extent
+    along the stream axis (t when t > 1, else c when c > 1, else z; `.axis`
+    is the xyzct index) is the CAPACITY, the most that may be appended.  The
+    other arguments are write_lfm's.  append() takes a numpy array or a CUDA
+    tensor (not both in one writer) of `count` indices along the axis; close()
+    finalises the file and returns the lfm_writer_stats dict.  The closed file
+    is byte-identical to write_lfm of the appended stack.  Leaving a `with`
+    block closes the writer, or aborts it (the file is removed) on an
+    exception; a writer dropped without close() is aborted too.  A file that
+    was never closed is not a valid .lfm."""
+
+    def __init__(self, path, shape, dtype=np.uint16, predictor_request=0, nnum=13, video=0, block_size=None,
+                 pixel_size=None, compression=1, metadata=None, device=-1, num_threads=-1):
+        shape = [int(v) for v in shape]
+        if not 1 <= len(shape) <= 5:
+            raise ValueError("Writer: shape is [t, c, z, y, x] or fewer leading dims")
+        shape = [1] * (5 - len(shape)) + shape
+        self._xyzct = shape[::-1]
+        self._dtype = np.dtype(dtype)
+        if device < 0 and _HAVE_TORCH and torch.cuda.is_available():
+            device = torch.cuda.current_device()
+        self._device = device
+        fn = _need("lfm_writer_open")
+        h = ctypes.c_void_p()
+        rc = fn(ctypes.byref(h), os.fsencode(path), _u32(self._xyzct), DTYPES[self._dtype],
+                (int(predictor_request) & 0x7F) | ((1 if video else 0) << 7), int(nnum),
+                _f32(pixel_size) if pixel_size is not None else None,
+                _u32(block_size) if block_size is not None else None, compression, _meta(metadata), int(device),
+                num_threads)
+        _check(rc, "lfm_writer_open")
+        self._h = h
+        self.axis = int(lib().lfm_writer_axis(h))
+        self._frame = shape[5 - self.axis:]  # the dims below the axis, [.., y, x]
+        self.stats = None
+
+    def _count(self, got):
+        want = [d for d in self._frame if d != 1]
+        got = [int(d) for d in got if d != 1]
+        if got == want:
+            return 1
+        if got[1:] == want:
+            return got[0]
+        raise ValueError("Writer.append: shape %s is neither %s nor (count,) + that" % (list(got), self._frame))
+
+    def append(self, a):
+        """Append a's indices along the stream axis: a numpy array or CUDA
+        tensor shaped like the stack below the axis, with an optional leading
+        count.  The data may be reused when the call returns."""
+        if self._h is None:
+            raise LfmError("Writer.append: the writer is closed")
+        if _HAVE_TORCH and isinstance(a, torch.Tensor) and a.is_cuda:
+            kt = Encoder._TORCH_KLB.get(str(a.dtype))
+            if kt != DTYPES[self._dtype] and not (DTYPES[self._dtype] == 1 and str(a.dtype) == "torch.int16"):
+                raise LfmError("Writer.append: tensor dtype %s, the stack holds %s" % (a.dtype, self._dtype))
+            if not a.is_contiguous():
+                raise LfmError("device input must be contiguous (got strides %s)" % (a.stride(),))
+            if self._device >= 0 and a.device.index != self._device:
+                raise LfmError("device input lives on cuda:%d, the writer on cuda:%d" % (a.device.index, self._device))
+            # (the library reads after the null stream's work: see Encoder._operand)
+            cur = torch.cuda.current_stream(a.device)
+            if cur != torch.cuda.default_stream(a.device):
+                cur.synchronize()
+            ptr, dev, shape = a.data_ptr(), 1, a.shape
+        else:
+            if _HAVE_TORCH and isinstance(a, torch.Tensor):
+                a = a.numpy()
+            a = np.ascontiguousarray(a)
+            if a.dtype != self._dtype:
+                raise LfmError("Writer.append: array dtype %s, the stack holds %s" % (a.dtype, self._dtype))
+            ptr, dev, shape = a.ctypes.data, 0, a.shape
+        count = self._count(shape)
+        _check(lib().lfm_writer_append(self._h, ptr, dev, count), "lfm_writer_append")
+        del a
+
+    def close(self):
+        """Finalise the file; returns the lfm_writer_stats dict (also `.stats`)."""
+        if self._h is None:
+            return self.stats
+        h, self._h = self._h, None
+        st = WriterStats()
+        _check(lib().lfm_writer_close(h, ctypes.byref(st)), "lfm_writer_close")
+        self.stats = st.as_dict()
+        return self.stats
+
+    def abort(self):
+        """Drop the writer and remove the file."""
+        if self._h is not None:
+            h, self._h = self._h, None
+            lib().lfm_writer_abort(h)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, exc_type, exc, tb):
+        if exc_type is None:
+            self.close()
+        else:
+            self.abort()
+        return False
+
+    def __del__(self):
+        try:
+            self.abort()
+        except Exception:
+            pass
+
+
+class Reader:
+    """lfm_reader: region reads of a .lfm file that fetch only the bytes of the
+    blocks the region depends on (open reads the header and the offset table).
+    .shape is [t, c, z, y, x]; .bytes_read counts every byte read from the
+    file so far, header and table included."""
+
+    def __init__(self, path):
+        fn = _need("lfm_reader_open")
+        h = ctypes.c_void_p()
+        self._h = None
+        _check(fn(ctypes.byref(h), os.fsencode(path)), "lfm_reader_open")
+        self._h = h
+        xyzct, bs = (ctypes.c_uint32 * 5)(), (ctypes.c_uint32 * 5)()
+        dt, hv, nn, fb = ctypes.c_int(), ctypes.c_uint8(), ctypes.c_uint8(), ctypes.c_uint64()
+        _check(lib().lfm_reader_info(h, xyzct, ctypes.byref(dt), bs, ctypes.byref(hv), ctypes.byref(nn),
+                                     ctypes.byref(fb)), "lfm_reader_info")
+        self._xyzct = list(xyzct)
+        self._dt = dt.value
+        self.shape = tuple(self._xyzct[::-1])
+        self.dtype = np.dtype(NP_OF[dt.value])
+        self.block_size = list(bs)
+        self.header_version = hv.value
+        self.nnum = nn.value
+        self.file_bytes = fb.value
+
+    @property
+    def bytes_read(self):
+        return int(lib().lfm_reader_bytes_read(self._h)) if self._h else 0
+
+    def read(self, lb, ub, device=None, out=None, return_stats=False, num_threads=-1):
+        """Region lb .. ub (inclusive, [x, y, z, c, t]) as an array [t, c, z, y, x]
+        of the region: numpy, or a torch CUDA tensor when `device` or a CUDA
+        tensor `out` is given (as decode_roi / decode_roi_device otherwise)."""
+        if self._h is None:
+            raise LfmError("Reader.read: the reader is closed")
+        lb, ub = [int(v) for v in lb], [int(v) for v in ub]
+        if len(lb) != 5 or len(ub) != 5 or any(u < l or l < 0 or u >= d for l, u, d in zip(lb, ub, self._xyzct)):
+            raise ValueError("Reader.read: region %s .. %s lies outside the image %s" % (lb, ub, self._xyzct))
+        shape = [u - l + 1 for l, u in zip(lb, ub)][::-1]
+        st = DecodeStats()
+        to_device = device is not None or (_HAVE_TORCH and isinstance(out, torch.Tensor))
+        if to_device:
+            out = _device_out("Reader.read", self._dt, shape, out, device)
+            ptr, nbytes = out.data_ptr(), out.numel() * out.element_size()
+        else:
+            if out is None:
+                out = np.empty(shape, dtype=self.dtype)
+            else:
+                if not isinstance(out, np.ndarray) or not out.flags.c_contiguous or not out.flags.writeable:
+                    raise ValueError("Reader.read: out must be a writeable C-contiguous numpy array")
+                if out.dtype != self.dtype or out.size != int(np.prod(shape)):
+                    raise ValueError("Reader.read: out holds %d x %s, the region is %s x %s"
+                                     % (out.size, out.dtype, shape, self.dtype))
+                out = out.reshape(shape)
+            ptr, nbytes = out.ctypes.data, out.nbytes
+        _check(lib().lfm_reader_read(self._h, _u32(lb), _u32(ub), ptr, nbytes, 1 if to_device else 0, num_threads,
+                                     ctypes.byref(st)), "lfm_reader_read")
+        return (out, st.as_dict()) if return_stats else out
+
+    def close(self):
+        if self._h is not None:
+            h, self._h = self._h, None
+            lib().lfm_reader_close(h)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, exc_type, exc, tb):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 # ------------------------------------------------------- multi-GPU reader --
