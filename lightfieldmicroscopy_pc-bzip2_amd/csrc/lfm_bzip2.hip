@@ -68,6 +68,7 @@
 #include "lfm_bwt_types.h"  // bwt_types8, bytes_eq, group_valid
 #include "lfm_bz_caps.h"  // rle_cap, out_cap, sel_cap, kGSize, align_up, max_parts
 #include "lfm_hip.h"
+#include "lfm_huff_heap.h"  // the heap steps of huff_lengths_heap
 
 #ifndef LFM_BWT_FORCE_FULL
 #define LFM_BWT_FORCE_FULL 0  // timing variants: every rotation sorted, no induction
@@ -3175,99 +3176,68 @@ __global__ __launch_bounds__(kHuffThreads) void huff_select_reg(Batch B)
 // (heap_narrow: weights < 2^17) use u32 entries (~1 KB of LDS per heap, so
 // many heaps are resident), the others u64 entries in a second launch over the
 // list the first one built (kList).
-//   * Entries sit in per-lane quads (entries 4q .. 4q + 3 contiguous): a
-//     node's children are half a quad, its grandchildren a whole quad, so a
-//     sift level reads the NEXT level's candidates (one ds_read_b128) while it
-//     decides the current one -- one LDS latency per level, not latency plus
-//     the compare chain.
-//   * The sift / upheap loops are uniform: every lane runs the level, selects
-//     instead of branches, one ballot per level (divergent per-lane exits cost
-//     ~20 scalar exec-mask instructions per level, and a CU's one scalar unit
-//     serves all its waves).
+//   * Entries are entry-major: entry e of every lane in one row of kL words,
+//     so a read or write of one entry index by all lanes has no bank conflict,
+//     an address is one multiply-add and a children pair one ds_read2.
+//   * The merges run in lockstep over the wave, one merge per trip, and a
+//     sift's path comes from the lane's pref bits (lfm_huff_heap.h), not from
+//     a walk: its levels are read in one LDS round trip and rewritten without
+//     a branch.  The level count is the wave's: from the largest heap, which
+//     shrinks by one entry per trip.
 //   * Parents go to global memory (the stream's code table, unused until
 //     huff_final) and come back for the depth pass, whose depths overlay the
 //     lane's own entries.
-template <typename Ent>
-struct HeapQuad {
-    Ent e[4];
+template <typename Ent, int kL>
+struct LdsHeap {
+    static constexpr uint32_t RS = sizeof(Ent) * kL;  // bytes per entry row
+    char* base;                                       // the lane's word of row 0
+    uint16_t* parent;
+    __device__ __forceinline__ Ent ld(uint32_t e) const { return *(const Ent*)(base + e * RS); }
+    __device__ __forceinline__ void st(uint32_t e, Ent v) const { *(Ent*)(base + e * RS) = v; }
+    __device__ __forceinline__ void ld_pair(uint32_t e, Ent& a, Ent& b) const
+    {
+        const char* q = base + e * RS;
+        a = *(const Ent*)q;
+        b = *(const Ent*)(q + RS);
+    }
+    __device__ __forceinline__ void fence() const { __builtin_amdgcn_sched_barrier(0); }
+    __device__ __forceinline__ void set_parent(uint32_t node, uint32_t p) const { parent[node] = (uint16_t)p; }
+    __device__ __forceinline__ bool any(bool b) const { return __builtin_amdgcn_ballot_w64(b) != 0; }
+    __device__ __forceinline__ void note_sift(uint32_t, uint32_t) const {}
+    __device__ __forceinline__ void note_push(uint32_t, uint32_t) const {}
+    __device__ __forceinline__ void check(const HeapPref&, uint32_t) const {}
 };
 
-// entries 0 .. 259, then one quad of sentinels (the grandchildren of every
-// node past 64 read as sentinels)
-constexpr int kHeapQuads = (kMaxAlpha + 2 + 3) / 4 + 1;
+// halvings after which every weight is 1 (the tree of equal weights is never
+// too long): the retry loop's bound
+template <typename Ent>
+constexpr int kHeapMaxRetries = sizeof(Ent) == 4 ? 17 : 32;
 
-// kL heaps with Ent entries in the LDS area hb (kHeapQuads * kL quads);
-// this lane's heap is (stream s, table tb)
+// kL heaps with Ent entries in the LDS area hb (kHeapEntries rows of kL
+// entries); this lane's heap is (stream s, table tb)
 template <typename Ent, int kL>
 __device__ __forceinline__ void heap_code_lengths(const Batch& B, char* hb, uint32_t lane, uint32_t s, uint32_t tb)
 {
-    constexpr int kQuads = kHeapQuads;
-    constexpr uint32_t QB = sizeof(HeapQuad<Ent>);   // bytes per lane per quad
-    constexpr uint32_t QS = QB * kL;                 // bytes per quad row
     constexpr uint32_t ES = sizeof(Ent);
-    const uint32_t lb = lane * QB;
-    auto ent = [&](uint32_t e) -> Ent& { return *(Ent*)(hb + (e >> 2) * QS + lb + (e & 3) * ES); };
+    static_assert(kHeapEntries * sizeof(Ent) * kL <= 33792, "the heaps' LDS grew");
+    static_assert(kHeapEntries >= kMaxAlpha + 2 && 2 * kMaxAlpha / (int)(ES / 2) < kHeapEntries, "heap entries");
     {
         const int A = (int)stream_nin(B, s) + 2;
         const uint32_t* freq = B.rfreq + ((size_t)s * kMaxGroups + tb) * kMaxAlpha;
         uint8_t* len = B.len + ((size_t)s * kMaxGroups + tb) * kMaxAlpha;
         uint16_t* parent = (uint16_t*)(B.code + ((size_t)s * kMaxGroups + tb) * kMaxAlpha);  // nodes 1 .. 2A - 2
+        LdsHeap<Ent, kL> acc{hb + lane * ES, parent};
+        auto ent = [&](uint32_t e) -> Ent& { return *(Ent*)(acc.base + e * LdsHeap<Ent, kL>::RS); };
         // depth of node k (<= 515): u16 number k % (ES / 2) of the lane's entry k / (ES / 2)
         auto dep = [&](uint32_t k) -> uint16_t& {
             return *(uint16_t*)((char*)&ent(k / (ES / 2)) + 2 * (k % (ES / 2)));
         };
         // rows are 8-byte aligned (258 words): pairs of words, a few loads ahead
         auto ld2 = [](const void* p, int i) { return *(const uint2*)((const uint32_t*)p + (i > 0 ? i : 0)); };
-        // a < b on weights (bits 10 and up) <=> a < (b with its node bits
-        // cleared) <=> (a with its node bits set) < b
-        constexpr Ent kW = ~(Ent)1023;
         // every position past the heap holds kSent (greater than any entry:
         // heights stop at 30), so the sift needs no bounds: a pop writes kSent
         // where the last entry was, a push overwrites the first one
         constexpr Ent kSent = ~(Ent)0;
-        // downheap from the root with key k; returns the new root.  Per level:
-        // the grandchildren quad is read first (it holds the children of
-        // either next node), then the level is decided from the children in
-        // registers; ea = address of the entry the key may land in, ca = the
-        // children pair of zz (ea of the next level is ca + 4 * right)
-        auto sift = [&](Ent k) {
-            const Ent kk = k | (Ent)1023;
-            uint32_t zz = 1, ea = lb + ES, ca = lb + 2u * ES;
-            Ent cx = ent(2), cy = ent(3), root = k;
-            bool go = true, first = true;
-            while (true) {
-                const uint32_t ga = min(zz, (uint32_t)kQuads - 1u) * QS + lb;
-                const HeapQuad<Ent> g = *(const HeapQuad<Ent>*)(hb + ga);
-                __builtin_amdgcn_sched_barrier(0);  // the read goes out before the level's compares
-                const uint32_t r = (cy | (Ent)1023) < cx ? 1u : 0u;
-                const Ent ky = r ? cy : cx;
-                go = go && !(kk < ky);
-                *(Ent*)(hb + ea) = ky;  // a stopped lane's stray write is overwritten below
-                if (first) root = go ? ky : k;
-                first = false;
-                const uint32_t zn = (zz << 1) | r, en = ca + r * ES;
-                ca = ga + r * (2u * ES);
-                ea = go ? en : ea;
-                zz = go ? zn : zz;
-                __builtin_amdgcn_sched_barrier(0);  // the quad is waited for last
-                cx = r ? g.e[2] : g.e[0];
-                cy = r ? g.e[3] : g.e[1];
-                if (!__builtin_amdgcn_ballot_w64(go)) break;
-            }
-            *(Ent*)(hb + ea) = k;
-            return root;
-        };
-        auto upheap = [&](uint32_t z, Ent k) {  // returns the final position
-            bool go = true;
-            while (true) {
-                const Ent up = ent(z >> 1);
-                go = go && k < (up & kW);  // the sentinel 0 stops it
-                ent(z) = go ? up : k;
-                z = go ? z >> 1 : z;
-                if (!__any(go)) break;
-            }
-            return z;
-        };
         // upheap for the initial inserts (z = i is the same in every lane
         // still inserting): the positions z >> j on the way to the root are
         // read at once, then every one is rewritten without a branch -- the
@@ -3290,63 +3260,61 @@ __device__ __forceinline__ void heap_code_lengths(const Batch& B, char* hb, uint
                 below = lt;
             }
         };
-        int retries = 0, nNodes = A;
-        while (true) {
-            // leaves at heap positions 1 .. A first (an insertion's upheap only
-            // touches positions below it), then inserted in order; sentinels
-            // past them
-            ent(0) = 0;
-            for (int q = (A + 1) >> 2; q < kQuads; ++q) {
+        // Rounds of the wave: a lane builds its heap (again, with halved
+        // weights, after a tree that came out too long), then all merge in
+        // lockstep; lanes whose heap is done sit the trips out.  Every loop's
+        // trip count is bounded by constants, whatever the entries hold.
+        int retries = 0;
+        uint32_t nMerged = (uint32_t)A;  // nodes so far
+        bool build = true;
+        for (int round = 0; round <= kHeapMaxRetries<Ent>; ++round) {
+            uint32_t nHeap = 1, tooLong = 0;
+            Ent top = 0;
+            HeapPref m;
+            if (build) {
+                // leaves at heap positions 1 .. A first (an insertion's upheap only
+                // touches positions below it), then inserted in order; sentinels
+                // past them
+                ent(0) = 0;
+                for (int e = A + 1; e < kHeapEntries; ++e) ent((uint32_t)e) = kSent;
+                // 32 frequencies per batch of 16 loads (one memory latency per
+                // batch, not per load: the compiler drains vmcnt at loop edges)
+                for (int i0 = 1; i0 <= A; i0 += 32) {
+                    uint2 f[16];
 #pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    if (4 * q + j > A) ent((uint32_t)(4 * q + j)) = kSent;
-            }
-            // 32 frequencies per batch of 16 loads (one memory latency per
-            // batch, not per load: the compiler drains vmcnt at loop edges)
-            for (int i0 = 1; i0 <= A; i0 += 32) {
-                uint2 f[16];
+                    for (int q = 0; q < 16; ++q) f[q] = ld2(freq, min(i0 - 1 + 2 * q, kMaxAlpha - 2));
 #pragma unroll
-                for (int q = 0; q < 16; ++q) f[q] = ld2(freq, min(i0 - 1 + 2 * q, kMaxAlpha - 2));
-#pragma unroll
-                for (int q = 0; q < 16; ++q) {
-                    const int i = i0 + 2 * q;
-                    uint32_t w0 = f[q].x ? f[q].x : 1u, w1 = f[q].y ? f[q].y : 1u;
-                    for (int r = 0; r < retries; ++r) {
-                        w0 = 1u + w0 / 2u;
-                        w1 = 1u + w1 / 2u;
+                    for (int q = 0; q < 16; ++q) {
+                        const int i = i0 + 2 * q;
+                        uint32_t w0 = f[q].x ? f[q].x : 1u, w1 = f[q].y ? f[q].y : 1u;
+                        for (int r = 0; r < retries; ++r) {
+                            w0 = 1u + w0 / 2u;
+                            w1 = 1u + w1 / 2u;
+                        }
+                        if (i <= A) ent(i) = ((Ent)w0 << 15) | (Ent)i;
+                        if (i + 1 <= A) ent(i + 1) = ((Ent)w1 << 15) | (Ent)(i + 1);
                     }
-                    if (i <= A) ent(i) = ((Ent)w0 << 15) | (Ent)i;
-                    if (i + 1 <= A) ent(i + 1) = ((Ent)w1 << 15) | (Ent)(i + 1);
                 }
+                for (int i = 1; i <= A; ++i) upheap_init((uint32_t)i);
+                heap_pref_build<Ent>(acc, m, (uint32_t)A);
+                nHeap = (uint32_t)A;
+                nMerged = (uint32_t)A;
+                top = ent(1);
             }
-            for (int i = 1; i <= A; ++i) upheap_init((uint32_t)i);
-            int nHeap = A;
-            nNodes = A;
-            uint32_t tooLong = 0;
-            Ent top = ent(1);
-            while (nHeap > 1) {
-                const Ent k1 = top;
-                const Ent l1 = ent(nHeap);
-                ent(nHeap) = kSent;
-                --nHeap;
-                const Ent k2 = sift(l1);
-                const Ent l2 = ent(nHeap);
-                ent(nHeap) = kSent;
-                --nHeap;
-                const Ent r2 = sift(l2);
-                ++nNodes;
-                parent[(uint32_t)k1 & 1023u] = (uint16_t)nNodes;
-                parent[(uint32_t)k2 & 1023u] = (uint16_t)nNodes;
-                const uint32_t h1 = (uint32_t)(k1 >> 10) & 31u, h2 = (uint32_t)(k2 >> 10) & 31u;
-                const uint32_t h = min(30u, 1u + max(h1, h2));
-                tooLong |= h > 17u ? 1u : 0u;
-                const Ent kn = ((((k1 >> 15) + (k2 >> 15)) << 5 | (Ent)h) << 10) | (Ent)nNodes;
-                ++nHeap;
-                top = upheap((uint32_t)nHeap, kn) == 1u ? kn : r2;
+            // the wave's largest heap, bit by bit
+            uint32_t hmax = 0;
+            for (int b = 8; b >= 0; --b) {
+                const uint32_t a = build ? (uint32_t)A : 0u;
+                if (__builtin_amdgcn_ballot_w64((a >> b & 1u) && (a >> (b + 1)) == (hmax >> (b + 1)))) hmax |= 1u << b;
             }
-            if (!tooLong) break;
-            ++retries;
+            hmax = min(__builtin_amdgcn_readfirstlane(hmax), (uint32_t)kMaxAlpha);
+            for (; hmax > 1u; --hmax)
+                if (build && nHeap > 1u) heap_merge_step_at<Ent>(acc, m, hmax, nHeap, nMerged, top, tooLong);
+            build = build && tooLong && retries < kHeapMaxRetries<Ent>;
+            if (build) ++retries;
+            if (!__builtin_amdgcn_ballot_w64(build)) break;
         }
+        const int nNodes = (int)nMerged;
         if (retries) atomicAdd(B.wide_cnt + 1, (uint32_t)retries);  // statistics (LFM_BZ2_STATS)
         // depths top-down (a parent is created after its children)
         dep(nNodes) = 0;
@@ -3388,7 +3356,7 @@ __device__ __forceinline__ void heap_code_lengths(const Batch& B, char* hb, uint
 template <int kL>
 __global__ __launch_bounds__(64) void huff_lengths_heap(Batch B, uint32_t nwg_wide, uint32_t nwide_streams)
 {
-    __shared__ HeapQuad<uint32_t> hq[kHeapQuads * kL];
+    __shared__ uint32_t hq[kHeapEntries * kL];
     char* hb = (char*)hq;
     const uint32_t lane = threadIdx.x;
     if (blockIdx.x >= nwg_wide) {
