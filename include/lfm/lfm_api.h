@@ -11,7 +11,9 @@
  *    host or a DEVICE-resident stack and reports per-stage timings (bench).
  *  - lfm_writer_* / lfm_reader_*: stacks larger than memory -- block layers
  *    appended over time to one .lfm file, and region reads that fetch only
- *    the bytes of the blocks they need (at the end of this file).
+ *    the bytes of the blocks they need (at the end of this file); the writer
+ *    checkpoints its table, so lfm_recover saves the complete layers of a
+ *    file that was never closed and a live reader reads them meanwhile.
  */
 #ifndef LFM_API_H
 #define LFM_API_H
@@ -255,7 +257,8 @@ typedef struct lfm_decode_stats {
  * stream may read it.  When it returns non-zero the buffer's contents are
  * unspecified.
  * Files the pipelined GPU decode does not take (compression NONE / ZLIB,
- * Nnum > 31, non-contiguous block offsets, LFM_GPU_DECODE=0 or
+ * Nnum > 31, non-contiguous block offsets, blocks more than one channel or
+ * time point deep, LFM_GPU_DECODE=0 or
  * LFM_GPU_BUNZIP2=0, device memory exhausted) are decoded on the host as
  * lfm_decode_memory does into a temporary and uploaded with one copy:
  * stats->path = 1.
@@ -374,8 +377,22 @@ LFM_API int lfm_decode_memory_multi_device(const uint8_t* buf, uint64_t len, voi
  * appended stack with the same arguments and xyzct[axis] = what was appended
  * (a final extent below blockSize[axis] included: that single layer is
  * encoded at close, with the block and the bzip2 level the one-shot writer
- * would clamp to).  A file that was never closed has a zero table and is NOT
- * a valid .lfm; there is no recovery of one.
+ * would clamp to).
+ *
+ * Checkpoints: whenever an encode of whole layers has finished and its payload
+ * is in the file, the writer also writes that range's entries into the
+ * capacity-sized table (payload first, then the entries; the first time also
+ * the chosen header byte at offset 0).  A file that was never closed is still
+ * NOT a valid .lfm -- its header says xyzct[axis] = capacity, its table ends in
+ * zeros, and lfm_reader_open refuses it with 2 -- but its complete layers are
+ * not lost: see lfm_recover, and lfm_reader_open_live to read them while the
+ * writer runs.
+ * lfm_writer_flush waits until every whole layer appended so far is encoded and
+ * its payload and table entries are in the file (both in-flight encodes are
+ * joined; the part of a layer the writer holds back stays in memory and is NOT
+ * covered).  sync != 0: fdatasync after that.  *committed (may be NULL) =
+ * indices along the stream axis a recovery would now keep.  A failed writer
+ * returns its code.
  * lfm_writer_close finalises and frees the writer whatever it returns; a
  * close with nothing appended returns 3 and removes the file.
  * lfm_writer_abort frees the writer and removes the file.  One writer is
@@ -389,7 +406,9 @@ typedef struct lfm_writer_stats {
     uint64_t moved_bytes;    /* payload bytes moved at close (0 when capacity reached) */
     uint64_t staged_peak_bytes; /* most input bytes the writer held back at one time  */
     int chosen, header_version; float entropy[8];
-    double total_ms;         /* wall clock spent inside append and close              */
+    double total_ms;         /* wall clock spent inside append, flush and close       */
+    uint64_t committed;      /* indices a recovery would keep (at close: appended); last: the
+                                fields before it lie where they lay before it existed  */
 } lfm_writer_stats;
 
 LFM_API int lfm_writer_open(lfm_writer** w, const char* filename, const uint32_t xyzct[KLB_DATA_DIMS], int dataType,
@@ -398,13 +417,59 @@ LFM_API int lfm_writer_open(lfm_writer** w, const char* filename, const uint32_t
                             const char metadata[KLB_METADATA_SIZE], int device, int numThreads);
 LFM_API int lfm_writer_axis(const lfm_writer* w);   /* 4, 3 or 2 */
 LFM_API int lfm_writer_append(lfm_writer* w, const void* img, int img_is_device, uint32_t count);
+LFM_API int lfm_writer_flush(lfm_writer* w, int sync, uint64_t* committed);
 LFM_API int lfm_writer_close(lfm_writer* w, lfm_writer_stats* stats);   /* finalises and frees */
 LFM_API void lfm_writer_abort(lfm_writer* w);                           /* frees, removes the file */
+
+/* ---- recovery: the .lfm of the complete layers of a file that was never closed ----
+ * Turns a file its writer never closed (a crash, a kill, a power loss) into
+ * the .lfm of its complete layers.  out_filename NULL: in place -- NOT atomic:
+ * an in-place recovery that is itself interrupted (while the payload moves
+ * down over the unused table entries, or before the truncate) can leave the
+ * file beyond repair, so recover into out_filename when the data matters and
+ * the space is there.  Else the input is only read and the result is written
+ * to out_filename.
+ * Committed prefix: the longest run of leading table entries that are
+ * non-zero, strictly increasing and end at or below the file's payload bytes
+ * (the payload starts behind the capacity-sized table), floored to whole
+ * layers along the stream axis.
+ * verify != 0: every stream of the committed layers is decoded, one layer at a
+ * time (memory is bounded by a layer): bzip2 streams are checked against their
+ * CRCs and the block's byte count, on the GPU decoder when a device is visible
+ * (with lfm_set_bunzip2_multiblock / lfm_set_bunzip2_periodic as set; streams
+ * the device hands back, and all of them without a device, go through the host
+ * library: stats.host_streams), ZLIB streams are inflated, and of NONE only the
+ * stored size can be checked.  The longest prefix of layers whose streams all
+ * pass is kept.  No inverse predictor runs: the file does not record the
+ * predictor family, and verification does not depend on lfm_set_family.
+ * verify == 0 trusts the table: safe after a process crash (the page cache
+ * survived), not after a power loss, where entries can reach the disk before
+ * their payload.
+ * The result is finalised as lfm_writer_close finalises (the same code) and is
+ * byte-identical to what the one-shot writer produces for the first
+ * stats.kept indices with the same arguments.
+ * Returns 0 on success -- also for a file that already is a closed .lfm:
+ * stats.already_valid = 1, nothing is done and no output is written; 2 when
+ * the file cannot be opened or is shorter than its table; 3 when no complete
+ * layer survives (the input is untouched, no output is created); 5 on write
+ * errors.  stats may be NULL. */
+typedef struct lfm_recover_stats {
+    int axis, header_version, already_valid;   /* already_valid: the file was a closed .lfm, nothing done */
+    uint64_t capacity, kept;                   /* indices along the axis: at open / in the result */
+    uint64_t committed_blocks;                 /* leading table entries that are plausible (above) */
+    uint64_t dropped_layers;                   /* committed layers not kept (torn, or failed verification) */
+    uint64_t verified_streams, host_streams;   /* streams decoded for verification; of them by the host library */
+    uint64_t bytes_written, moved_bytes;
+    double total_ms;
+} lfm_recover_stats;
+LFM_API int lfm_recover(const char* filename, const char* out_filename, int verify, int numThreads,
+                        lfm_recover_stats* stats);
 
 /* ---- ranged reader: region reads that fetch only the bytes they need ----
  * lfm_reader_open reads the fixed header and the offset table, nothing else
  * (2: the file cannot be opened, is truncated, or its table points past its
- * end -- a file its writer never closed).  lfm_reader_read decodes the region
+ * end -- a file its writer never closed: see lfm_recover and
+ * lfm_reader_open_live).  lfm_reader_read decodes the region
  * lb .. ub (inclusive, xyzct) as lfm_decode_memory_roi (out_is_device == 0)
  * or lfm_decode_memory_roi_device (!= 0) do -- the same blocks, return codes,
  * device ordering and lfm_decode_stats (stats may be NULL) -- but the streams
@@ -414,9 +479,33 @@ LFM_API void lfm_writer_abort(lfm_writer* w);                           /* frees
  * the region in its frames, plus the frame before an odd z of a video stack.
  * A region equal to the whole image is allowed.  lfm_reader_bytes_read is the
  * cumulative count of bytes read from the file, header and table included.
- * One reader is used by one thread at a time. */
+ * One reader is used by one thread at a time.
+ *
+ * Live reader.  lfm_reader_open_live also takes a file its writer has not
+ * closed (on a closed file it is lfm_reader_open).  The reader then shows the
+ * committed whole layers, found by lfm_recover's rule: lfm_reader_info reports
+ * xyzct[axis] as that extent, which may be 0; a region past it returns 3, and
+ * inside it lfm_reader_read works as on a closed file, host and device
+ * destinations alike (the same blocks, lfm_decode_stats and bytes_read
+ * accounting; the payload starts behind the capacity-sized table).
+ * lfm_reader_refresh re-reads the fixed header and the table entries not yet
+ * accepted (one pread each, both counted in bytes_read) and gives the extent
+ * now readable.  If the writer has closed the file meanwhile (the header's
+ * extent differs from the capacity, or the table is complete) the reader
+ * re-parses it as a closed file; on a closed file refresh only reports the
+ * extent.  A reader MUST refresh after the writer's close before it reads
+ * again, and reads that overlap the close (its payload move) are unsupported;
+ * after a refresh that returns non-zero (2: the file could not be read as
+ * either) the reader is good for lfm_reader_close only.
+ * A stream that is bad although its entry is plausible (entries that reached
+ * the disk before their payload) surfaces as return code 2 through the bzip2
+ * CRC, never as wrong pixels; files of compression NONE carry no checksum and
+ * lack this guarantee.  One reader is used by one thread; a writer and a
+ * reader of the same file may live in different threads or processes. */
 typedef struct lfm_reader lfm_reader;
 LFM_API int lfm_reader_open(lfm_reader** r, const char* filename);        /* header + table only */
+LFM_API int lfm_reader_open_live(lfm_reader** r, const char* filename);
+LFM_API int lfm_reader_refresh(lfm_reader* r, uint32_t* extent);
 LFM_API int lfm_reader_info(const lfm_reader* r, uint32_t xyzct[KLB_DATA_DIMS], int* dataType,
                             uint32_t blockSize[KLB_DATA_DIMS], uint8_t* headerVersion, uint8_t* Nnum,
                             uint64_t* file_bytes);

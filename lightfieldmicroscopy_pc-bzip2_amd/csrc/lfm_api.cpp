@@ -385,6 +385,18 @@ extern "C" int lfm_writer_append(lfm_writer* w, const void* img, int img_is_devi
     return w ? w->w.append(img, img_is_device != 0, count) : 3;
 }
 
+extern "C" int lfm_writer_flush(lfm_writer* w, int sync, uint64_t* committed)
+{
+    if (!w) return 3;
+    return w->w.flush(sync != 0, committed);
+}
+
+extern "C" int lfm_recover(const char* filename, const char* out_filename, int verify, int numThreads,
+                           lfm_recover_stats* stats)
+{
+    return lfm::recover_file(filename, out_filename, verify != 0, numThreads, stats);
+}
+
 extern "C" int lfm_writer_close(lfm_writer* w, lfm_writer_stats* stats)
 {
     if (!w) return 3;
@@ -400,19 +412,25 @@ extern "C" void lfm_writer_abort(lfm_writer* w)
     delete w;
 }
 
-extern "C" int lfm_reader_open(lfm_reader** r, const char* filename)
+static int reader_open(lfm_reader** r, const char* filename, bool live)
 {
     if (!r) return 3;
     *r = nullptr;
     if (!filename) return 3;
     lfm_reader* p = new lfm_reader;
-    if (int rc = p->r.open(filename)) {
+    if (int rc = p->r.open(filename, live)) {
         delete p;
         return rc;
     }
     *r = p;
     return 0;
 }
+
+extern "C" int lfm_reader_open(lfm_reader** r, const char* filename) { return reader_open(r, filename, false); }
+
+extern "C" int lfm_reader_open_live(lfm_reader** r, const char* filename) { return reader_open(r, filename, true); }
+
+extern "C" int lfm_reader_refresh(lfm_reader* r, uint32_t* extent) { return r ? r->r.refresh(extent) : 3; }
 
 extern "C" int lfm_reader_info(const lfm_reader* r, uint32_t xyzct[KLB_DATA_DIMS], int* dataType,
                                uint32_t blockSize[KLB_DATA_DIMS], uint8_t* headerVersion, uint8_t* Nnum,

@@ -519,6 +519,8 @@ static int gpu_decode(const uint8_t* payload, size_t len, const klb_image_header
     const uint64_t nb = g.nblocks;
     const uint32_t block_bytes = h.getBlockSizeBytes();
     if (!nb || !block_bytes || nb >= (1ull << 31)) return -1;
+    // (a chunk's frames, DecodePlan::frames, are those of blocks one channel and one time point deep)
+    if (g.bs[3] != 1 || g.bs[4] != 1) return -1;
     // (the scatter's and the inverse predictor's 16-byte rows)
     if (dd && ((uintptr_t)img & 15)) return -1;
     Timeline tl;

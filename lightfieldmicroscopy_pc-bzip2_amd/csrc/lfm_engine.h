@@ -416,7 +416,11 @@ void release_decode_workers();
 // Encoder::submit / wait on an encoder of its own, two in flight; the calling
 // thread is the in-order writer: a finished range's payload is appended to
 // the file and its block sizes re-accumulated into the offset table, which
-// close writes with the final extent.
+// close writes with the final extent.  A range of whole layers is also a
+// checkpoint: once its payload is in the file, its table entries go into the
+// capacity-sized table (and, the first time, the chosen header byte to offset
+// 0), so a file that is never closed holds what recover_file and a live
+// FileReader need to find its complete layers.
 class StreamWriter {
 public:
     // h: the stack as lfm_writer_open describes it, xyzct[axis] the capacity
@@ -425,6 +429,9 @@ public:
     int open(const char* filename);
     int axis() const { return axis_; }
     int append(const void* img, bool dev, uint32_t count);
+    // joins the encodes in flight (their payload and table entries are then in
+    // the file), fdatasync when asked; *committed = indices a recovery keeps
+    int flush(bool sync, uint64_t* committed);
     int close(lfm_writer_stats* st);  // the writer is finished either way
     void abort();                     // closes and removes the file
 
@@ -450,24 +457,55 @@ private:
     std::vector<uint8_t> h_buf_[3];  // host: held-back part, assembled range, raw frame before the next range
     DeviceBuffer d_buf_[3];          // device: the same
     std::vector<uint64_t> pending_;  // tickets in flight, oldest first
+    std::vector<uint64_t> pending_n_;  // their indices along the axis
     std::vector<uint64_t> table_;    // block end offsets so far
     uint64_t payload_ = 0, payload_base_ = 0, nb_cap_ = 0;
+    bool hv_on_disk_ = false;        // the chosen header byte has been checkpointed
     lfm_writer_stats st_{};
 };
 
+// What an unclosed file's table says (recover_file and the live FileReader
+// apply the same rule): the committed prefix is the longest run of leading
+// entries that are non-zero, strictly increasing and end inside the payload
+// bytes the file holds (`payload_bytes` = file size - payload base); only
+// whole block layers of it count.  `from`: entries below it are known good.
+struct CommittedPrefix {
+    uint64_t blocks = 0;        // plausible leading entries
+    uint64_t layer_blocks = 0;  // blocks of one layer along the stream axis
+    uint64_t layers = 0;        // whole layers among `blocks`
+};
+CommittedPrefix committed_prefix(const klb_image_header& capacity_header, int axis, const uint64_t* table, uint64_t nb,
+                                 uint64_t payload_bytes, uint64_t from = 0);
+
+// lfm_recover: the .lfm of the complete layers of a file its writer never
+// closed, finalised by the code StreamWriter::close finalises with.
+int recover_file(const char* filename, const char* out_filename, bool verify, int threads, lfm_recover_stats* st);
+
 // lfm_reader: header and table in memory, the streams of a region's blocks
-// fetched from the file by byte range (PayloadSource) for each read.
+// fetched from the file by byte range (PayloadSource) for each read.  A live
+// reader (open with live = true) takes a file its writer has not closed: `h` is
+// then the view of the committed whole layers (xyzct[axis] may be 0), the
+// payload starts behind the capacity-sized table, and refresh() extends the
+// view by what the writer has checkpointed since.
 class FileReader {
 public:
     ~FileReader();
-    int open(const char* filename);
+    int open(const char* filename, bool live = false);
+    int refresh(uint32_t* extent);
     int read(const uint32_t lb[5], const uint32_t ub[5], void* out, uint64_t out_bytes, bool dev, int threads,
              lfm_decode_stats* stats);
     klb_image_header h;
     uint64_t file_bytes = 0, bytes_read = 0;
 
 private:
+    int load(bool* closed);          // header and table into h; *closed: the table is a closed file's
+    void make_view();                // live: h from cap_ and the entries accepted so far
     int fd_ = -1;
+    bool live_ = false;              // the file was unclosed when last looked at
+    int axis_ = 2;
+    klb_image_header cap_;           // live: the header as on disk (xyzct[axis] the capacity) and its table as far as read
+    uint64_t known_ = 0;             // live: leading entries of cap_'s table accepted so far (whole layers)
+    uint64_t payload_base_ = 0;      // file offset of the payload
 };
 
 } // namespace lfm

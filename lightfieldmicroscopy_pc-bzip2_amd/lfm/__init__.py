@@ -45,6 +45,7 @@ EXPORTS = [
     "lfm_set_bunzip2_periodic", "lfm_get_bunzip2_periodic",
     "lfm_writer_open", "lfm_writer_axis", "lfm_writer_append", "lfm_writer_close", "lfm_writer_abort",
     "lfm_reader_open", "lfm_reader_info", "lfm_reader_read", "lfm_reader_bytes_read", "lfm_reader_close",
+    "lfm_writer_flush", "lfm_recover", "lfm_reader_open_live", "lfm_reader_refresh",
     # lfm_hip.h
     "lfm_hip_predict", "lfm_hip_unpredict", "lfm_hip_unpredict_async", "lfm_hip_unpredict_check",
     "lfm_hip_unpredict_path",
@@ -111,12 +112,24 @@ class WriterStats(ctypes.Structure):
                 ("host_streams", ctypes.c_uint64), ("bzip2_blocks", ctypes.c_uint64),
                 ("bytes_written", ctypes.c_uint64), ("moved_bytes", ctypes.c_uint64),
                 ("staged_peak_bytes", ctypes.c_uint64), ("chosen", ctypes.c_int), ("header_version", ctypes.c_int),
-                ("entropy", ctypes.c_float * 8), ("total_ms", ctypes.c_double)]
+                ("entropy", ctypes.c_float * 8), ("total_ms", ctypes.c_double), ("committed", ctypes.c_uint64)]
 
     def as_dict(self):
         d = {f: getattr(self, f) for f, _ in self._fields_ if f != "entropy"}
         d["entropy"] = list(self.entropy)
         return d
+
+
+class RecoverStats(ctypes.Structure):
+    """lfm_recover_stats (lfm_api.h)."""
+    _fields_ = [("axis", ctypes.c_int), ("header_version", ctypes.c_int), ("already_valid", ctypes.c_int),
+                ("capacity", ctypes.c_uint64), ("kept", ctypes.c_uint64), ("committed_blocks", ctypes.c_uint64),
+                ("dropped_layers", ctypes.c_uint64), ("verified_streams", ctypes.c_uint64),
+                ("host_streams", ctypes.c_uint64), ("bytes_written", ctypes.c_uint64),
+                ("moved_bytes", ctypes.c_uint64), ("total_ms", ctypes.c_double)]
+
+    def as_dict(self):
+        return {f: getattr(self, f) for f, _ in self._fields_}
 
 
 _lib = None
@@ -290,6 +303,16 @@ def lib():
         L.lfm_reader_bytes_read.restype = ctypes.c_uint64
         L.lfm_reader_close.argtypes = [vp]
         L.lfm_reader_close.restype = None
+    # checkpoints, recovery and the live reader, likewise
+    if hasattr(L, "lfm_writer_flush"):
+        L.lfm_writer_flush.argtypes = [vp, ctypes.c_int, ctypes.POINTER(ctypes.c_uint64)]
+    if hasattr(L, "lfm_recover"):
+        L.lfm_recover.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_int, ctypes.c_int,
+                                  ctypes.POINTER(RecoverStats)]
+    if hasattr(L, "lfm_reader_open_live"):
+        L.lfm_reader_open_live.argtypes = [ctypes.POINTER(vp), ctypes.c_char_p]
+    if hasattr(L, "lfm_reader_refresh"):
+        L.lfm_reader_refresh.argtypes = [vp, u32p]
     _lib = L
     return L
 
@@ -786,7 +809,9 @@ class Writer:
     is byte-identical to write_lfm of the appended stack.  Leaving a `with`
     block closes the writer, or aborts it (the file is removed) on an
     exception; a writer dropped without close() is aborted too.  A file that
-    was never closed is not a valid .lfm."""
+    was never closed (the process died) is not a valid .lfm, but the writer
+    checkpoints its table: recover() turns such a file into the .lfm of its
+    complete layers, and Reader(path, live=True) reads them meanwhile."""
 
     def __init__(self, path, shape, dtype=np.uint16, predictor_request=0, nnum=13, video=0, block_size=None,
                  pixel_size=None, compression=1, metadata=None, device=-1, num_threads=-1):
@@ -851,6 +876,18 @@ class Writer:
         _check(lib().lfm_writer_append(self._h, ptr, dev, count), "lfm_writer_append")
         del a
 
+    def flush(self, sync=False):
+        """Wait until every whole layer appended so far is in the file, payload
+        and table entries (lfm_writer_flush); sync=True also fdatasyncs.
+        Returns the indices along the axis that recover() would now keep and a
+        live Reader shows after refresh(); the part of a layer the writer
+        holds back is not among them."""
+        if self._h is None:
+            raise LfmError("Writer.flush: the writer is closed")
+        committed = ctypes.c_uint64()
+        _check(_need("lfm_writer_flush")(self._h, 1 if sync else 0, ctypes.byref(committed)), "lfm_writer_flush")
+        return int(committed.value)
+
     def close(self):
         """Finalise the file; returns the lfm_writer_stats dict (also `.stats`)."""
         if self._h is None:
@@ -888,14 +925,26 @@ class Reader:
     """lfm_reader: region reads of a .lfm file that fetch only the bytes of the
     blocks the region depends on (open reads the header and the offset table).
     .shape is [t, c, z, y, x]; .bytes_read counts every byte read from the
-    file so far, header and table included."""
+    file so far, header and table included.
 
-    def __init__(self, path):
-        fn = _need("lfm_reader_open")
+    live=True (lfm_reader_open_live) also takes a file whose Writer has not
+    closed it: .shape then shows the committed whole layers along the stream
+    axis (0 before the first), refresh() picks up what the writer has
+    checkpointed since (Writer.flush), and a region past the extent raises
+    LfmError code 3.  After the writer's close, refresh() before reading on."""
+
+    def __init__(self, path, live=False):
+        name = "lfm_reader_open_live" if live else "lfm_reader_open"
+        fn = _need(name)
         h = ctypes.c_void_p()
         self._h = None
-        _check(fn(ctypes.byref(h), os.fsencode(path)), "lfm_reader_open")
+        self._live = bool(live)
+        _check(fn(ctypes.byref(h), os.fsencode(path)), name)
         self._h = h
+        self._info()
+
+    def _info(self):
+        h = self._h
         xyzct, bs = (ctypes.c_uint32 * 5)(), (ctypes.c_uint32 * 5)()
         dt, hv, nn, fb = ctypes.c_int(), ctypes.c_uint8(), ctypes.c_uint8(), ctypes.c_uint64()
         _check(lib().lfm_reader_info(h, xyzct, ctypes.byref(dt), bs, ctypes.byref(hv), ctypes.byref(nn),
@@ -909,6 +958,17 @@ class Reader:
         self.nnum = nn.value
         self.file_bytes = fb.value
 
+    def refresh(self):
+        """Look at the file again (lfm_reader_refresh): a live reader takes up
+        the layers the writer has committed since, or the closed file when the
+        writer has closed it meanwhile.  Returns the shape, as `.shape` now is."""
+        if self._h is None:
+            raise LfmError("Reader.refresh: the reader is closed")
+        extent = ctypes.c_uint32()
+        _check(_need("lfm_reader_refresh")(self._h, ctypes.byref(extent)), "lfm_reader_refresh")
+        self._info()
+        return self.shape
+
     @property
     def bytes_read(self):
         return int(lib().lfm_reader_bytes_read(self._h)) if self._h else 0
@@ -920,7 +980,9 @@ class Reader:
         if self._h is None:
             raise LfmError("Reader.read: the reader is closed")
         lb, ub = [int(v) for v in lb], [int(v) for v in ub]
-        if len(lb) != 5 or len(ub) != 5 or any(u < l or l < 0 or u >= d for l, u, d in zip(lb, ub, self._xyzct)):
+        # (a live reader's extent is the library's to judge: a region past it is its code 3)
+        if len(lb) != 5 or len(ub) != 5 or any(u < l or l < 0 or (u >= d and not self._live)
+                                               for l, u, d in zip(lb, ub, self._xyzct)):
             raise ValueError("Reader.read: region %s .. %s lies outside the image %s" % (lb, ub, self._xyzct))
         shape = [u - l + 1 for l, u in zip(lb, ub)][::-1]
         st = DecodeStats()
@@ -960,6 +1022,23 @@ class Reader:
             self.close()
         except Exception:
             pass
+
+
+def recover(path, out=None, verify=True, num_threads=-1):
+    """Turn a file its Writer never closed into the .lfm of its complete layers
+    (lfm_recover): in place when `out` is None -- not atomic, an interrupted
+    in-place recovery can leave the file beyond repair -- else `path` is only
+    read and the result written to `out`.  verify=True decodes every stream of
+    the committed layers (bzip2 CRCs and lengths; on the GPU when one is
+    visible) and keeps the longest prefix of layers that pass; verify=False
+    trusts the table, which is only safe after a process crash.  Returns the
+    lfm_recover_stats dict (`kept` indices along the axis; `already_valid` for
+    a closed file, which is left alone); LfmError code 3 when no complete
+    layer survives."""
+    st = RecoverStats()
+    _check(_need("lfm_recover")(os.fsencode(path), os.fsencode(out) if out is not None else None,
+                                1 if verify else 0, num_threads, ctypes.byref(st)), "lfm_recover")
+    return st.as_dict()
 
 
 # ------------------------------------------------------- multi-GPU reader --
