@@ -77,6 +77,14 @@ int lfm_hip_predict_candidates(const uint16_t* d_frame, uint16_t* d_out7, int W,
  * chunks, klb_imageIO.cpp:2030-2093).  Synchronous: writes the float result
  * (without the 0.96 raw-candidate factor) to *entropy. */
 int lfm_hip_entropy2d(const uint16_t* d_cand, uint64_t npix, float* entropy, void* stream);
+/* Test / diagnostic entry: the integer bigram histograms the selection kernels
+ * count for d_cands[0..ncand) (a host array of 1..8 device buffers of npix
+ * symbols each, any 2-byte alignment), before any float arithmetic:
+ * d_hist[ncand][nchunks][65536] with nchunks = ceil(npix / 450000) and bin =
+ * (val << 8) | partner.  Bins 0 and 0xFFFF and the sentinel's bigram are
+ * included; the end-of-L element has none.  Same launches and counting code as
+ * lfm_hip_entropy2d / lfm_hip_select.  Synchronous. */
+int lfm_hip_entropy2d_hist(const uint16_t* const* d_cands, int ncand, uint64_t npix, uint32_t* d_hist, void* stream);
 
 /* Predictor selection on one frame: builds the 8 candidates (0 = raw,
  * k = predictor k, spatial), their 2D entropies (candidate 0 scaled by 0.96)

@@ -34,6 +34,8 @@
 //              64 rows x 256 u32 counters in LDS, written by nobody else, so
 //              no 16-bit packing, no merge and no global atomics -- then the
 //              -P logf P terms and the ascending row sums of its 64 rows
+//              (ent_rows<true>, behind lfm_hip_entropy2d_hist, stores the
+//              counters instead: the tests compare them bin for bin)
 //   host     : per job the 256 row sums are combined in the oracle's fixed
 //              order (lfm_oracle.c lfmo_entropy_chunk: the 64 rows of a
 //              quarter by an xor butterfly, quarters left to right) -- the
@@ -228,13 +230,19 @@ __global__ __launch_bounds__(256) void ent_link(Jobs J, uint8_t* __restrict__ pa
 // position of the job, then writes the 64 row sums rows[job][r].  The
 // quarters of a job are blocks b, b + 8, b + 16, b + 24 (one XCD: the job's
 // bytes are read from one L2).  Bin 0 -- (0, 0), the high bytes of small
-// symbols -- is counted in registers.
+// symbols -- is counted in registers.  kDump (lfm_hip_entropy2d_hist): the
+// same counting, then the counters go to hist[job][65536] and nothing else is
+// computed; run_entropy launches ent_rows<false>.
 #ifndef LFM_ENT_ROW_THREADS
 #define LFM_ENT_ROW_THREADS 1024  // (512: a config-3 selection 0.51 ms, 1 024: 0.50; profiles/r06_ab_select_ent_rows.txt)
 #endif
 constexpr int kRowThreads = LFM_ENT_ROW_THREADS;
+template <bool kDump> struct RowsOut { typedef float type; };     // rows[job][256]
+template <> struct RowsOut<true> { typedef uint32_t type; };      // hist[job][65536]
+template <bool kDump>
 __global__ __launch_bounds__(kRowThreads) void ent_rows(Jobs J, const uint8_t* __restrict__ part,
-                                                        const uint32_t* __restrict__ meta, float* __restrict__ rows)
+                                                        const uint32_t* __restrict__ meta,
+                                                        typename RowsOut<kDump>::type* __restrict__ rows)
 {
     extern __shared__ uint32_t cnt[];  // 64 rows x kRow
     __shared__ uint32_t zsum;
@@ -277,6 +285,13 @@ __global__ __launch_bounds__(kRowThreads) void ent_rows(Jobs J, const uint8_t* _
     __syncthreads();
     if (q == 0 && threadIdx.x == 0) cnt[0] += zsum;
     __syncthreads();
+    if constexpr (kDump) {  // the counters as they stand, and nothing below
+        for (int o = threadIdx.x; o < 64 * 256; o += kRowThreads) {
+            const int m = o >> 8, b = o & 255;
+            rows[(size_t)job * 65536 + (size_t)(4 * m + q) * 256 + b] = cnt[m * kRow + b];
+        }
+        return;
+    }
     // -P logf P per bin in place (bin 0xFFFF is never summed by the
     // reference), then row sums in ascending bin order
     const float fs = (float)S;
@@ -326,12 +341,18 @@ static size_t workspace_layout(uint64_t npix, int ncand, bool with_cands, Worksp
     return off;
 }
 
-static hipError_t run_entropy(const Jobs& J, const Workspace& w, hipStream_t st)
+// ent_next, ent_link, then ent_rows into w.rows -- or, with d_hist, its
+// counters into d_hist[njobs][65536] (lfm_hip_entropy2d_hist)
+static hipError_t run_entropy(const Jobs& J, const Workspace& w, hipStream_t st, uint32_t* d_hist = nullptr)
 {
     hipLaunchKernelGGL(ent_next, dim3(kSegMax, J.njobs), dim3(256), 0, st, J, w.part, w.tab);
     hipLaunchKernelGGL(ent_link, dim3(J.njobs), dim3(256), 0, st, J, w.part, w.tab, w.meta);
     const uint32_t nblk = (uint32_t)((J.njobs + 7) / 8) * 32;
-    hipLaunchKernelGGL(ent_rows, dim3(nblk), dim3(kRowThreads), 64 * kRow * 4, st, J, w.part, w.meta, w.rows);
+    if (d_hist)
+        hipLaunchKernelGGL(ent_rows<true>, dim3(nblk), dim3(kRowThreads), 64 * kRow * 4, st, J, w.part, w.meta, d_hist);
+    else
+        hipLaunchKernelGGL(ent_rows<false>, dim3(nblk), dim3(kRowThreads), 64 * kRow * 4, st, J, w.part, w.meta,
+                           w.rows);
     return hipGetLastError();
 }
 
@@ -357,14 +378,20 @@ static float combine_rows(const float* part)
 
 using namespace lfm;
 
-static int entropy_impl(const uint16_t* const* cands, int ncand, uint64_t npix, float* out, void* dws,
-                        bool own_ws, hipStream_t st)
+static Jobs make_jobs(const uint16_t* const* cands, int ncand, uint64_t npix)
 {
     Jobs J{};
     for (int k = 0; k < ncand; ++k) J.cand[k] = (const uint8_t*)cands[k];
     J.npix = npix;
     J.nchunks = (int)((npix + kChunkPix - 1) / kChunkPix);
     J.njobs = J.nchunks * ncand;
+    return J;
+}
+
+static int entropy_impl(const uint16_t* const* cands, int ncand, uint64_t npix, float* out, void* dws,
+                        bool own_ws, hipStream_t st)
+{
+    const Jobs J = make_jobs(cands, ncand, npix);
     Workspace w{};
     workspace_layout(npix, ncand, false, &w, (uint8_t*)dws);
     if (run_entropy(J, w, st) != hipSuccess) return LFM_HIP_ERUNTIME;
@@ -393,6 +420,25 @@ extern "C" int lfm_hip_entropy2d(const uint16_t* d_cand, uint64_t npix, float* e
     int rc = entropy_impl(c, 1, npix, entropy, ws, true, st);
     (void)hipFreeAsync(ws, st);
     return rc;
+}
+
+extern "C" int lfm_hip_entropy2d_hist(const uint16_t* const* d_cands, int ncand, uint64_t npix, uint32_t* d_hist,
+                                      void* stream)
+{
+    if (!d_cands || ncand < 1 || ncand > 8 || !npix || !d_hist) return LFM_HIP_EINVAL;
+    for (int k = 0; k < ncand; ++k)
+        if (!d_cands[k]) return LFM_HIP_EINVAL;
+    hipStream_t st = (hipStream_t)stream;
+    const size_t bytes = workspace_layout(npix, ncand, false, nullptr, nullptr);
+    void* ws = nullptr;
+    if (hipMallocAsync(&ws, bytes, st) != hipSuccess) return LFM_HIP_ERUNTIME;
+    const Jobs J = make_jobs(d_cands, ncand, npix);
+    Workspace w{};
+    workspace_layout(npix, ncand, false, &w, (uint8_t*)ws);
+    hipError_t e = run_entropy(J, w, st, d_hist);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    (void)hipFreeAsync(ws, st);
+    return e == hipSuccess ? LFM_HIP_OK : LFM_HIP_ERUNTIME;
 }
 
 extern "C" size_t lfm_hip_select_workspace_bytes(int W, int H)

@@ -49,7 +49,8 @@ EXPORTS = [
     # lfm_hip.h
     "lfm_hip_predict", "lfm_hip_unpredict", "lfm_hip_unpredict_async", "lfm_hip_unpredict_check",
     "lfm_hip_unpredict_path",
-    "lfm_hip_predict_candidates", "lfm_hip_entropy2d", "lfm_hip_select_workspace_bytes", "lfm_hip_select",
+    "lfm_hip_predict_candidates", "lfm_hip_entropy2d", "lfm_hip_entropy2d_hist", "lfm_hip_select_workspace_bytes",
+    "lfm_hip_select",
     "lfm_hip_synth", "lfm_hip_device_count", "lfm_hip_force_generic", "lfm_hip_bzip2_workspace_bytes", "lfm_hip_bzip2_out_cap",
     "lfm_hip_bzip2_blocks", "lfm_hip_bzip2_last_stage_ms", "lfm_hip_bunzip2_workspace_bytes", "lfm_hip_bunzip2_blocks", "lfm_hip_scatter_blocks",
     "lfm_hip_crop_region", "lfm_hip_bzip2_workspace_bytes_multi", "lfm_hip_bzip2_max_count_multi",
@@ -206,6 +207,7 @@ def lib():
     L.lfm_hip_unpredict_check.argtypes = [ctypes.c_int]
     L.lfm_hip_predict_candidates.argtypes = [vp, vp] + [ctypes.c_int] * 4 + [vp]
     L.lfm_hip_entropy2d.argtypes = [vp, ctypes.c_uint64, f32p, vp]
+    L.lfm_hip_entropy2d_hist.argtypes = [ctypes.POINTER(vp), ctypes.c_int, ctypes.c_uint64, vp, vp]
     L.lfm_hip_bzip2_workspace_bytes.argtypes = [ctypes.c_uint32, ctypes.c_uint32]
     L.lfm_hip_bzip2_workspace_bytes.restype = ctypes.c_size_t
     L.lfm_hip_bzip2_out_cap.argtypes = [ctypes.c_uint32]
@@ -1237,6 +1239,22 @@ def entropy_device(d_cand, npix=None, stream=None):
     n = d_cand.numel() if npix is None else npix
     _check(lib().lfm_hip_entropy2d(d_cand.data_ptr(), n, ctypes.byref(e), _stream(stream)), "lfm_hip_entropy2d")
     return e.value
+
+
+def entropy_hist_device(d_cands, npix, stream=None):
+    """lfm_hip_entropy2d_hist: the integer bigram histograms the selection
+    kernels count for a list of 1..8 int16 device tensors (views at any 2-byte
+    offset) of at least npix symbols each, as a (ncand, nchunks, 65536) uint32
+    array, bin = (val << 8) | partner."""
+    ncand, nchunks = len(d_cands), -(-int(npix) // 450000)
+    if not 1 <= ncand <= 8 or npix < 1 or any(str(t.dtype) != "torch.int16" or t.numel() < npix or
+                                              not t.is_contiguous() for t in d_cands):
+        raise ValueError("entropy_hist_device: 1..8 contiguous int16 tensors of npix >= 1 symbols each")
+    ptrs = (ctypes.c_void_p * ncand)(*[t.data_ptr() for t in d_cands])
+    d_hist = torch.empty((ncand, nchunks, 65536), dtype=torch.int32, device=d_cands[0].device)
+    _check(lib().lfm_hip_entropy2d_hist(ptrs, ncand, npix, d_hist.data_ptr(), _stream(stream)),
+           "lfm_hip_entropy2d_hist")
+    return d_hist.cpu().numpy().view(np.uint32)
 
 
 def set_bzip2_multiblock(on):

@@ -58,6 +58,9 @@ def lib():
         L.lfmo_unpredict_frame.restype = ctypes.c_int
         L.lfmo_entropy2d.argtypes = [u16p, ctypes.c_uint64]
         L.lfmo_entropy2d.restype = ctypes.c_float
+        L.lfmo_entropy_chunk.argtypes = [ctypes.POINTER(ctypes.c_uint8), ctypes.c_uint32,
+                                         ctypes.POINTER(ctypes.c_uint32)]
+        L.lfmo_entropy_chunk.restype = ctypes.c_float
         L.lfmo_select.argtypes = [u16p] + [ctypes.c_int] * 4 + [ctypes.POINTER(ctypes.c_float)]
         L.lfmo_select.restype = ctypes.c_int
         L.lfmo_residual.argtypes = [u16p, u16p] + [ctypes.c_int] * 8
@@ -150,6 +153,23 @@ def unpredict_volume(sym, T, family, k, video):
 def entropy2d(cand):
     cand = np.ascontiguousarray(cand, dtype=np.uint16).ravel()
     return float(lib().lfmo_entropy2d(_p16(cand), cand.size))
+
+
+CHUNK_PIX = 450000  # lfmo_entropy2d's block
+
+
+def bigram_hist(cand):
+    """The integer histograms lfmo_entropy_chunk fills for the 450000-pixel
+    chunks of a candidate buffer, before any float arithmetic: (nchunks, 65536)
+    uint32, bin = (L[j] << 8) | L[j+1]."""
+    cand = np.ascontiguousarray(cand, dtype=np.uint16).ravel()
+    nchunks = -(-cand.size // CHUNK_PIX)
+    out = np.zeros((nchunks, 65536), dtype=np.uint32)
+    for q in range(nchunks):
+        c = cand[q * CHUNK_PIX:(q + 1) * CHUNK_PIX].view(np.uint8)
+        lib().lfmo_entropy_chunk(c.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), c.size,
+                                 out[q].ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)))
+    return out
 
 
 def select(frame, T, family):
