@@ -1464,15 +1464,18 @@ __device__ __forceinline__ void place_slot(const Tabs& P, uint32_t mode, uint32_
 // indices) and all of one kind are issued before any is used: one memory
 // round trip for the values and one for the text of all IPT items (under
 // per-item branches the compiler waited for each item's loads in turn: 2 IPT
-// round trips).
-template <int TH, int IPT>
+// round trips).  BLOCKED: item q is slot t * IPT + q instead, the arrangement
+// the block sort takes (IPT consecutive values per lane: the same lines, and
+// no exchange through LDS afterwards).
+template <int TH, int IPT, bool BLOCKED>
 __device__ __forceinline__ void chunk_load(const Batch& B, uint32_t cb, uint32_t m, uint32_t t, uint64_t (&k)[IPT],
                                            uint32_t (&v)[IPT])
 {
     const uint32_t s = cb / B.cap, n = B.n[s];
     const uint8_t* T = B.T + (size_t)s * B.cap;
+    auto slot = [&](int q) { return BLOCKED ? t * IPT + q : q * TH + t; };
 #pragma unroll
-    for (int q = 0; q < IPT; ++q) v[q] = B.vals_a[cb + min(q * TH + t, m ? m - 1u : 0u)];
+    for (int q = 0; q < IPT; ++q) v[q] = B.vals_a[cb + min(slot(q), m ? m - 1u : 0u)];
     uint32_t d[IPT][3];
 #pragma unroll
     for (int q = 0; q < IPT; ++q) {
@@ -1484,7 +1487,7 @@ __device__ __forceinline__ void chunk_load(const Batch& B, uint32_t cb, uint32_t
     }
 #pragma unroll
     for (int q = 0; q < IPT; ++q) {
-        const uint32_t j = q * TH + t, i = v[q] & kIdxMask;
+        const uint32_t j = slot(q), i = v[q] & kIdxMask;
         if (j >= m) {
             k[q] = ~0ull;
             v[q] = 0u;
@@ -1501,8 +1504,8 @@ __device__ __forceinline__ void chunk_load(const Batch& B, uint32_t cb, uint32_t
 // The chunk's keys / values are loaded striped (element q * TH + t: coalesced),
 // sorted (rocPRIM block merge sort: thread t ends with sorted positions
 // t * IPT .. t * IPT + IPT - 1), the still-tied flags come from the
-// neighbours in registers (each thread's edge keys through LDS), and sa /
-// uflag go back striped through LDS.  The sorted keys are not stored: the few
+// neighbours in registers (each thread's edge keys through LDS), and (without
+// PLACE) sa / uflag go back striped through LDS.  The sorted keys are not stored: the few
 // consumers (tie groups) recompute them from the text (rot_key8).
 //
 // PLACE: the workgroup also places its rotations (place_slot) from the blocked
@@ -1512,9 +1515,18 @@ __device__ __forceinline__ void chunk_load(const Batch& B, uint32_t cb, uint32_t
 // and not carried through it: a second value word would make rocPRIM's merge
 // passes move 8-byte values.  Tied slots are placed in the provisional order;
 // bwt_place_tied places them again once tie_runs_direct has ordered them.
+// A placing sort loads blocked (chunk_load: no exchange) and writes sa only at
+// its tied slots, which it appends to the tied list `tl` itself (length *tcnt,
+// at most tcap entries): nothing after it on that path reads sa or uflag
+// anywhere else.  A workgroup's entries are in slot order and contiguous (one
+// atomic add per workgroup), which is what tie_runs_direct needs to see a run:
+// a run never leaves its bucket, hence never its chunk.  When a run is left to
+// the text rounds, which do read every slot, first_round sorts again without
+// PLACE.
 template <int TH, int IPT, bool PLACE>
 __global__ __launch_bounds__(TH) void bwt_chunk_sort(Batch B, const uint32_t* __restrict__ cbp,
-                                                     const uint32_t* __restrict__ cep, uint32_t nch, uint32_t per)
+                                                     const uint32_t* __restrict__ cep, uint32_t nch, uint32_t per,
+                                                     uint32_t* __restrict__ tl, uint32_t* __restrict__ tcnt, uint32_t tcap)
 {
     // per > 0: XCD-aware order (workgroup b runs on XCD b % 8; chunks
     // x * per .. x * per + per - 1, consecutive and mostly of one stream, all
@@ -1530,6 +1542,9 @@ __global__ __launch_bounds__(TH) void bwt_chunk_sort(Batch B, const uint32_t* __
         uint64_t first[TH], last[TH];
         uint32_t sv[NI];
         uint8_t fl[NI];
+        // PLACE: whether a wave holds a tied slot, the tied counts per wave, the workgroup's place in the tied list
+        alignas(16) uint32_t wany[TH / 64];
+        uint32_t wsum[TH / 64], base;
     };
     __shared__ union alignas(16) {
         typename Sort::storage_type s;
@@ -1540,15 +1555,20 @@ __global__ __launch_bounds__(TH) void bwt_chunk_sort(Batch B, const uint32_t* __
     __shared__ std::conditional_t<PLACE, PlaceTabs, char> P;
     const uint32_t cb = cbp[c], ce = cep[c], m = ce - cb, t = threadIdx.x;
     const uint32_t s = cb / B.cap, mode = PLACE ? B.bwt_mode[s] : 0u;
-    if constexpr (PLACE) place_tabs_load(B, s, mode, P, t);  // (published by the barriers of the sort)
+    // (the tables are published by the barrier after the sort, below: their
+    // first use is place_slot in the epilogue, and with the blocked load no
+    // barrier stands ahead of the sort's own)
+    if constexpr (PLACE) place_tabs_load(B, s, mode, P, t);
     uint64_t k[IPT];
     uint32_t v[IPT];
-    chunk_load<TH, IPT>(B, cb, m, t, k, v);
-    // the sort's valid-item count refers to the blocked arrangement
-    ExK().striped_to_blocked(k, k, sm.ek);
-    __syncthreads();
-    ExV().striped_to_blocked(v, v, sm.ev);
-    __syncthreads();
+    chunk_load<TH, IPT, PLACE>(B, cb, m, t, k, v);
+    if constexpr (!PLACE) {
+        // the sort's valid-item count refers to the blocked arrangement
+        ExK().striped_to_blocked(k, k, sm.ek);
+        __syncthreads();
+        ExV().striped_to_blocked(v, v, sm.ev);
+        __syncthreads();
+    }
     Sort().sort(k, v, sm.s, m);
     __syncthreads();
     sm.x.first[t] = k[0];
@@ -1565,31 +1585,50 @@ __global__ __launch_bounds__(TH) void bwt_chunk_sort(Batch B, const uint32_t* __
         nt += f ? 1u : 0u;
         fpack |= (uint64_t)(f ? 1u : 0u) << (8 * q);
     }
-    if constexpr (IPT == 2) {
-        *(uint2*)&sm.x.sv[t * IPT] = make_uint2(v[0], v[1]);
-        *(uint16_t*)&sm.x.fl[t * IPT] = (uint16_t)fpack;
-    } else {
+    if constexpr (PLACE) {
+        const uint8_t* T = B.T + (size_t)s * B.cap;
+        uint32_t w0[IPT], w1[IPT];
 #pragma unroll
-        for (int q = 0; q < IPT; q += 4) *(uint4*)&sm.x.sv[t * IPT + q] = make_uint4(v[q], v[q + 1], v[q + 2], v[q + 3]);
-        if constexpr (IPT == 8) *(uint64_t*)&sm.x.fl[t * IPT] = fpack;
-        else *(uint32_t*)&sm.x.fl[t * IPT] = (uint32_t)fpack;
-    }
-    __syncthreads();
-    [[maybe_unused]] const uint8_t* T = B.T + (size_t)s * B.cap;
-    [[maybe_unused]] uint32_t w0[IPT], w1[IPT];
-    if constexpr (PLACE) {  // (items past m hold value 0: the loads stay inside the text)
-#pragma unroll
-        for (int q = 0; q < IPT; ++q) {
+        for (int q = 0; q < IPT; ++q) {  // (items past m hold value 0: the loads stay inside the text)
             const uint32_t* w = place_text_at(T, v[q] & kIdxMask);
             w0[q] = w[0];
             w1[q] = w[1];
         }
-    }
-    for (uint32_t j = t; j < m; j += TH) {
-        B.sa[cb + j] = sm.x.sv[j];
-        B.uflag[cb + j] = sm.x.fl[j];
-    }
-    if constexpr (PLACE) {
+        // The tied slots, while the text loads are under way.  The branch is
+        // uniform: a word per wave in LDS and one barrier.  Thread t's entries
+        // follow those of the threads below it.
+        const uint32_t lane = t & 63u, wave = t >> 6;
+        const uint32_t wave_tied = __any(nt) ? 1u : 0u;
+        if (lane == 0) sm.x.wany[wave] = wave_tied;
+        __syncthreads();
+        uint32_t any_tied = 0;
+#pragma unroll
+        for (uint32_t w = 0; w < (uint32_t)TH / 64; ++w) any_tied |= sm.x.wany[w];
+        if (any_tied) {
+            uint32_t inc = nt;
+            for (int d = 1; d < 64; d <<= 1) {
+                const uint32_t a = __shfl_up(inc, d);
+                if ((int)lane >= d) inc += a;
+            }
+            if (lane == 63) sm.x.wsum[wave] = inc;
+            __syncthreads();
+            uint32_t at = inc - nt, tot = 0;
+            for (uint32_t w = 0; w < (uint32_t)TH / 64; ++w) {
+                if (w < wave) at += sm.x.wsum[w];
+                tot += sm.x.wsum[w];
+            }
+            if (t == 0) sm.x.base = atomicAdd(tcnt, tot);
+            __syncthreads();
+            at += sm.x.base;
+#pragma unroll
+            for (int q = 0; q < IPT; ++q) {
+                if ((fpack >> (8 * q)) & 1u) {
+                    B.sa[cb + t * IPT + q] = v[q];
+                    if (at < tcap) tl[at] = cb + t * IPT + q;
+                    ++at;
+                }
+            }
+        }
         const size_t o = (size_t)s * B.cap;
         const uint32_t n = B.n[s], j0 = cb - (uint32_t)o + t * IPT;
         uint8_t* LL = (uint8_t*)B.mtfv + o;
@@ -1602,6 +1641,21 @@ __global__ __launch_bounds__(TH) void bwt_chunk_sort(Batch B, const uint32_t* __
                 place_slot(P, mode, j0 + q, v[q], x, (uint32_t)(k[q] >> 56), LL, E, B.orig_ptr + s);
             }
         }
+        return;
+    }
+    if constexpr (IPT == 2) {
+        *(uint2*)&sm.x.sv[t * IPT] = make_uint2(v[0], v[1]);
+        *(uint16_t*)&sm.x.fl[t * IPT] = (uint16_t)fpack;
+    } else {
+#pragma unroll
+        for (int q = 0; q < IPT; q += 4) *(uint4*)&sm.x.sv[t * IPT + q] = make_uint4(v[q], v[q + 1], v[q + 2], v[q + 3]);
+        if constexpr (IPT == 8) *(uint64_t*)&sm.x.fl[t * IPT] = fpack;
+        else *(uint32_t*)&sm.x.fl[t * IPT] = (uint32_t)fpack;
+    }
+    __syncthreads();
+    for (uint32_t j = t; j < m; j += TH) {
+        B.sa[cb + j] = sm.x.sv[j];
+        B.uflag[cb + j] = sm.x.fl[j];
     }
     if (__any(nt)) {
         for (int d = 32; d > 0; d >>= 1) nt += __shfl_xor(nt, d);
@@ -4028,9 +4082,9 @@ size_t prim_tmp_bytes(uint32_t count, uint32_t cap)
 
 // The parts of the workspace that are not per-stream kernel buffers.
 // cnt: eight device counters, zeroed at the start of every BWT attempt:
-//   [0]    chunks of class 0 (<= kSmallCap) from the bucket pass; from
-//          tie_offsets on, the length of the tied list (rewritten by every
-//          round's compaction)
+//   [0]    chunks of class 0 (<= kSmallCap) from the bucket pass; from the
+//          placing chunk sorts (which count up from 0) or tie_offsets on, the
+//          length of the tied list (rewritten by every round's compaction)
 //   [1]    chunks of class 1 (<= kBigCap); then the length of the compacted
 //          group keys of a text round
 //   [2]    chunks of class 2 (rocPRIM segmented sort)
@@ -4170,6 +4224,8 @@ struct TieRounds {
     bool none_left;      // a count read 0 and no kernel ran since: skip the later reads
     BwtStats stats;
     uint64_t* gk;        // text rounds' group keys: u64 per entry in the rank area, free until the ranks are built
+    uint32_t first[8] = {};   // the counters after placing sorts that left no run, read by first_round
+    bool first_read = false;  // ... and valid: text_rounds does not read them again
 
     // the tied list's length, read back: one host synchronisation
     hipError_t read_count(uint32_t* out, size_t bytes = 4)
@@ -4182,13 +4238,19 @@ struct TieRounds {
 uint32_t list_grid(uint32_t cnt) { return std::min<uint32_t>(4096, (cnt + 255) / 256); }
 
 // the nc chunks of class `cls`, in XCD-aware order: workgroup b runs on XCD b % 8
+// (place: the sorts also append their tied slots to tl, at most tcap of them, and count them in W.cnt[0])
 template <int TH, int IPT>
-void chunk_sorts(const Batch& B, const ChunkLists& CL, int cls, uint32_t nc, bool place, hipStream_t st)
+void chunk_sorts(const Batch& B, const ChunkLists& CL, int cls, uint32_t nc, bool place, const TieRounds& W, uint32_t* tl,
+                 uint32_t tcap)
 {
     const uint32_t per = (nc + 7) / 8;
     if (!nc) return;
-    if (place) hipLaunchKernelGGL((bwt_chunk_sort<TH, IPT, true>), dim3(8 * per), dim3(TH), 0, st, B, CL.b[cls], CL.e[cls], nc, per);
-    else hipLaunchKernelGGL((bwt_chunk_sort<TH, IPT, false>), dim3(8 * per), dim3(TH), 0, st, B, CL.b[cls], CL.e[cls], nc, per);
+    if (place)
+        hipLaunchKernelGGL((bwt_chunk_sort<TH, IPT, true>), dim3(8 * per), dim3(TH), 0, W.st, B, CL.b[cls], CL.e[cls], nc,
+                           per, tl, W.cnt, tcap);
+    else
+        hipLaunchKernelGGL((bwt_chunk_sort<TH, IPT, false>), dim3(8 * per), dim3(TH), 0, W.st, B, CL.b[cls], CL.e[cls], nc,
+                           per, nullptr, nullptr, 0u);
 }
 
 // Round 0: the bucket pass, the chunk sorts by the 8-byte prefix (one host
@@ -4208,9 +4270,7 @@ hipError_t first_round(const Batch& B, TieRounds& W)
     CL.cnt = W.cnt;
     CL.cnt3 = W.cnt + 5;
     uint32_t nch[6] = {0, 0, 0, 0, 0, 0};
-    if ((e = hipMemsetAsync(W.cnt, 0, 32, st)) != hipSuccess ||
-        (e = hipMemsetAsync(B.done, 0, (size_t)count * 4, st)) != hipSuccess)
-        return e;
+    if ((e = hipMemsetAsync(W.cnt, 0, 32, st)) != hipSuccess) return e;
     hipLaunchKernelGGL(bwt_bucket<kBucketBits>, dim3(count), dim3(kBucketThreads), 0, st, B, CL);
     if ((e = hipGetLastError()) != hipSuccess || (e = W.read_count(nch, 24)) != hipSuccess) return e;
     W.stats.chunks[0] = nch[5];
@@ -4221,15 +4281,47 @@ hipError_t first_round(const Batch& B, TieRounds& W)
     // The sorts place their rotations themselves (PLACE) when the batch is
     // induced and every chunk goes through them: the segmented sort's keys
     // lie in keys_a, where the entries go.  Between the sorts and bwt_induce
-    // only tie_offsets (done), tie_compact (cl0), tie_runs_direct (sa, cnt[7])
-    // and the two small kernels below run on that path, and none of them
-    // writes keys_a or mtfv (the symbols); a text round would (its scratch is
-    // both), which is why a call that runs one places the whole batch again.
+    // only tie_runs_direct (sa at tied slots, cnt[7]) and the two small
+    // kernels below run on that path, and none of them writes keys_a or mtfv
+    // (the symbols); a text round would (its scratch is both), which is why a
+    // call that runs one places the whole batch again.
     const bool fused = !B.it_full && nch[2] == 0;
     W.stats.fused_sorts = fused;
-    chunk_sorts<kTinyCap / kCsItems, kCsItems>(B, CL, 3, nch[5], fused, st);
-    chunk_sorts<kCsThreads, kCsItems>(B, CL, 0, nch[0], fused, st);
-    chunk_sorts<kBigThreads, kBigItems>(B, CL, 1, nch[1], fused, st);
+    W.first_read = false;
+    auto sorts = [&](bool place, uint32_t* tl) {
+        chunk_sorts<kTinyCap / kCsItems, kCsItems>(B, CL, 3, nch[5], place, W, tl, (uint32_t)W.N);
+        chunk_sorts<kCsThreads, kCsItems>(B, CL, 0, nch[0], place, W, tl, (uint32_t)W.N);
+        chunk_sorts<kBigThreads, kBigItems>(B, CL, 1, nch[1], place, W, tl, (uint32_t)W.N);
+    };
+    W.covered = kKeyBytes;
+    W.none_left = false;
+    if (fused) {
+        // The placing sorts list their tied slots themselves, in the vals_b
+        // area (N entries; the text rounds' and free here: the chunk lists in
+        // cl0 / cl1 are still being read), and write sa at those slots only.
+        // cnt[0] held the chunk count of class 0; from here on it is the
+        // list's length.
+        uint32_t* tl = B.vals_b;
+        if ((e = hipMemsetAsync(W.cnt, 0, 4, st)) != hipSuccess) return e;
+        sorts(true, tl);
+        hipLaunchKernelGGL(tie_runs_direct, dim3(1024), dim3(256), 0, st, B, tl, W.cnt, W.cnt + 7);
+        // queued ahead of the host's read of the counts; void if a run was left (place_path)
+        hipLaunchKernelGGL(bwt_place_tied, dim3(256), dim3(256), 0, st, B, tl, W.cnt);
+        hipLaunchKernelGGL(bwt_pend_live, dim3(count), dim3(256), 0, st, B);
+        if ((e = hipGetLastError()) != hipSuccess || (e = W.read_count(W.first, 32)) != hipSuccess) return e;
+        W.stats.first_ties = W.first[0];
+        W.stats.left_runs = W.first[7];
+        if (W.first[7] == 0) {  // every run sorted: text_rounds takes the counts from W.first
+            W.first_read = true;
+            return hipSuccess;
+        }
+        // A run was left to the text rounds, which read sa and uflag at every
+        // slot: the sorts once more without PLACE, from vals_a and the chunk
+        // lists (both intact), then the tied list as on the unfused path.
+        if ((e = hipMemsetAsync(W.cnt + 7, 0, 4, st)) != hipSuccess) return e;
+    }
+    if ((e = hipMemsetAsync(B.done, 0, (size_t)count * 4, st)) != hipSuccess) return e;
+    sorts(false, nullptr);
     if (nch[2]) {
         hipLaunchKernelGGL(bwt_chunk_keys, dim3(nch[2]), dim3(256), 0, st, B, CL.b[2], CL.e[2]);
         e = rocprim::segmented_radix_sort_pairs(W.tmp, W.tmp_bytes, B.keys_a, B.keys_b, B.vals_a, B.sa,
@@ -4243,12 +4335,6 @@ hipError_t first_round(const Batch& B, TieRounds& W)
     hipLaunchKernelGGL(tie_offsets, dim3(1), dim3(1024), 0, st, B, W.cnt);
     hipLaunchKernelGGL(tie_compact, dim3(count), dim3(256), 0, st, B, B.cl0);
     hipLaunchKernelGGL(tie_runs_direct, dim3(1024), dim3(256), 0, st, B, B.cl0, W.cnt, W.cnt + 7);
-    if (fused) {  // queued ahead of the host's read of the counts; void if a run was left (place_path)
-        hipLaunchKernelGGL(bwt_place_tied, dim3(256), dim3(256), 0, st, B, B.cl0, W.cnt);
-        hipLaunchKernelGGL(bwt_pend_live, dim3(count), dim3(256), 0, st, B);
-    }
-    W.covered = kKeyBytes;
-    W.none_left = false;
     return hipGetLastError();
 }
 
@@ -4262,10 +4348,12 @@ hipError_t text_rounds(const Batch& B, TieRounds& W)
     for (int r = 0; r < kTextRounds; ++r) {
         // counters: [0] tied slots, [7] runs tie_runs_direct left (read with the first round's count)
         uint32_t c8[8] = {};
-        hipError_t e = W.read_count(c8, r == 0 ? 32 : 4);
+        hipError_t e = hipSuccess;
+        if (r == 0 && W.first_read) std::copy(W.first, W.first + 8, c8);  // first_round has read them (placing sorts)
+        else e = W.read_count(c8, r == 0 ? 32 : 4);
         if (e != hipSuccess) return e;
         const uint32_t cnt = c8[0];
-        if (r == 0) {
+        if (r == 0 && !W.stats.fused_sorts) {  // (placing sorts: the first attempt's, set by first_round)
             W.stats.first_ties = cnt;
             W.stats.left_runs = c8[7];
         }
