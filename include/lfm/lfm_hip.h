@@ -145,6 +145,13 @@ uint64_t lfm_hip_bzip2_last_blocks(void);
  * run, [10] 1 when streams still tied after the last round were flagged as
  * periodic, [11] 0. */
 void lfm_hip_bzip2_last_bwt_stats(uint32_t out[12]);
+/* The sort jobs of that call's last attempt: slot ranges of whole buckets
+ * sorted by one workgroup each, per sorter capacity (at most 512 rotations, at
+ * most 1 024, at most 2 048, at most 4 096).  A chunk is one job, or two where
+ * a chunk of several buckets and more than 512 rotations is sorted as its
+ * slots before its last bucket and that bucket; the segmented-sort class is
+ * not among them. */
+void lfm_hip_bzip2_last_sort_jobs(uint32_t out[4]);
 /* How the sorted rotations of the calling thread's last lfm_hip_bzip2_blocks
  * or lfm_hip_bzip2_blocks_multi were placed in the final order (read-only,
  * decided from the counts above): 0 not at all (the batch was sorted again

@@ -774,7 +774,8 @@ constexpr uint32_t kKeyBytes = 8;  // first-round key: the 8-byte prefix (0.02 %
 //                  of < 2 kChunk rotations (a cut after the bucket that holds
 //                  each multiple of kChunk; a bucket larger than kChunk is a
 //                  chunk of its own).
-//  bwt_chunk_sort  one workgroup per chunk: the chunk's rotations sorted by the
+//  bwt_chunk_sort  one workgroup per sort job (a chunk, or one of the two parts
+//                  of a multi-bucket chunk: ChunkLists): its rotations sorted by the
 //                  whole key in LDS (buckets are ordered by the key's top bits,
 //                  so sorting a run of whole buckets sorts each bucket), and
 //                  the still-tied flags (equal keys never cross a bucket).
@@ -788,7 +789,7 @@ constexpr uint32_t kBucketBits = 14;               // 64 KiB histogram, two work
                                                    // buckets overflow the small sorter)
 constexpr int kBucketThreads = 1024;               // each walks 8 positions of a tile (kBktG, kBktTile below)
 constexpr uint32_t kChunk = 1024;  // (512 equal, 2 048 slower end to end in round 5)
-constexpr int kCsThreads = 512, kCsItems = 4;      // chunks up to 2 048 (every multi-bucket chunk); 512 x 4 measured
+constexpr int kCsThreads = 512, kCsItems = 4;      // jobs up to 2 048 (single buckets above kChunk); 512 x 4 measured
                                                    // 10 % faster than 256 x 8
 constexpr int kBigThreads = 512, kBigItems = 8;    // single buckets up to 4 096
 constexpr uint32_t kSmallCap = kCsThreads * kCsItems, kBigCap = kBigThreads * kBigItems;
@@ -799,16 +800,45 @@ constexpr uint32_t kMaxCuts = 1024;                // cut entries a stream may n
                                                    // < 185 000); a longer stream that does need kMaxCuts entries or
                                                    // more is flagged for the host library (bwt_bucket)
 
-// chunk lists: [3] <= kTinyCap, [0] <= kSmallCap, [1] <= kBigCap, [2] larger
-// (rocPRIM segmented sort)
+// chunk classes by size: [3] <= kTinyCap, [0] <= kSmallCap, [1] <= kBigCap,
+// [2] larger (rocPRIM segmented sort).  The classes are counted; what the
+// sorters run over are the sort jobs below.
 constexpr uint32_t kTinyCap = 1024;  // half-size sorter: the ~40 % of chunks at most
                                      // this long would pad a kSmallCap sort to twice their size
+constexpr uint32_t kMiniCap = 512;   // quarter-size sorter (sort jobs only)
+
+// Sort jobs: slot ranges [b, e) of whole buckets, one workgroup each, listed
+// by the smallest sorter that holds them.  A chunk is one job, except that a
+// chunk of several buckets and more than kMiniCap rotations which cuts_of
+// closed after its last bucket is two: the slots before that bucket, and the
+// bucket.  Such a chunk's earlier buckets lie between two multiples of kChunk
+// and its last bucket is at most kChunk, so both parts fit the half-size
+// sorter, where the whole chunk (1.2 kChunk on average on light-field symbols)
+// padded a kSmallCap sort; the sorters cost their capacity, not their content.
+// A job never cuts a bucket, so equal keys stay inside one workgroup.
+// (The chunks that end at nsub or in front of a bucket above kChunk hold no
+// multiple of kChunk: at most kChunk rotations, one job.)
+// Lists: [0] <= kSmallCap (single buckets only), [1] <= kBigCap and [2] larger
+// (the chunks of classes 1 and 2, one job each: their counters are the class
+// counters), [3] <= kTinyCap, [4] <= kMiniCap.
+constexpr int kJobLists = 5;
 struct ChunkLists {
-    uint32_t* b[4];
-    uint32_t* e[4];
-    uint32_t* cnt;   // counters of classes 0..2
-    uint32_t* cnt3;  // counter of class 3
+    uint32_t* b[kJobLists];
+    uint32_t* e[kJobLists];
+    uint32_t* cnt;  // the workspace's counters (Scratch)
 };
+// counter words (Scratch::cnt) of the job lists, and of the two classes that have no list of their own
+__device__ __host__ constexpr uint32_t job_cnt_word(uint32_t list)
+{
+    return list == 0 ? 6u : list == 1 ? 1u : list == 2 ? 2u : list == 3 ? 4u : 3u;
+}
+__device__ __forceinline__ uint32_t job_list(uint32_t m)
+{
+    return m <= kMiniCap ? 4u : (m <= kTinyCap ? 3u : (m <= kSmallCap ? 0u : (m <= kBigCap ? 1u : 2u)));
+}
+// A cut entry (a slot below 2^20) that closes a chunk after a bucket of at
+// most kChunk carries that bucket's size - 1 above the slot, and a flag.
+constexpr uint32_t kCutSlotBits = 20, kCutSlotMask = (1u << kCutSlotBits) - 1u, kCutHasLast = 1u << 30;
 
 // A tile of the text for the bucket pass: T[i0 - 1 .. i0 + m + 8) cyclically
 // in tile[kTOff - 1 .. kTOff + m + 8), m = min(n - i0, kBktTile) (T[i0 + k]
@@ -965,7 +995,8 @@ __global__ __launch_bounds__(kBucketThreads) __attribute__((amdgpu_waves_per_eu(
     __shared__ __attribute__((aligned(16))) uint8_t tile[kTOff + kBktTile + 8];  // (a last group's 16 bytes end here)
     __shared__ uint32_t cuts[kMaxCuts];
     __shared__ uint32_t wsum[kBucketThreads / 64], wcut[kBucketThreads / 64];
-    __shared__ uint32_t ccount[4], cbase[4];
+    __shared__ uint32_t ccount[2];  // chunks of class 0 and of class 3 (classes 1 and 2 are job lists 1 and 2)
+    __shared__ uint32_t jcount[kJobLists], jbase[kJobLists];
     __shared__ uint32_t sinuse[8];                  // bytes present in the RLE1 text (the stream's inUse map)
     __shared__ uint32_t cnt_u[256], cnt_s[256];     // unsorted / sorted rotations per first byte
     __shared__ uint32_t cnt_l[256];                 // unsorted rotations that induce ("live"), per first byte
@@ -976,7 +1007,8 @@ __global__ __launch_bounds__(kBucketThreads) __attribute__((amdgpu_waves_per_eu(
     const uint32_t n = B.n[s];
     const uint8_t* T = B.T + (size_t)s * B.cap;
     const uint32_t o = s * B.cap;
-    if (t < 4) ccount[t] = 0;
+    if (t < 2) ccount[t] = 0;
+    if (t < (uint32_t)kJobLists) jcount[t] = 0;
     if (t < 8) sinuse[t] = 0;
     // histogram of the BITS-bit bucket over the rotations to sort; the pass
     // restarts (at most twice) for the B rotations when they are clearly fewer
@@ -1080,7 +1112,7 @@ __global__ __launch_bounds__(kBucketThreads) __attribute__((amdgpu_waves_per_eu(
                     if (off) emit(off);
                     emit(e);
                 } else if ((e - 1) / kChunk >= (off + kChunk - 1) / kChunk && e - 1 >= kChunk) {
-                    emit(e);
+                    emit(e | ((c - 1u) << kCutSlotBits) | kCutHasLast);
                 }
             }
             off += c;
@@ -1179,23 +1211,42 @@ __global__ __launch_bounds__(kBucketThreads) __attribute__((amdgpu_waves_per_eu(
         }
     }
     __syncthreads();
-    // chunks = runs between consecutive cuts (the last ends at nsub)
+    // chunks = runs between consecutive cuts (the last ends at nsub), counted
+    // by class; each gives one sort job or two (see ChunkLists)
     const uint32_t nch = min(tcut, kMaxCuts - 1) + 1;
-    uint32_t cb = 0, ce = 0, cls = 0, slot = 0;
+    // this lane's chunk [cb, ce): jobs [cb, mid) and, where mid < ce, [mid, ce)
+    uint32_t cb = 0, mid = 0, ce = 0, l0 = 0, l1 = 0, s0 = 0, s1 = 0;
     if (t < nch) {
-        cb = t ? cuts[t - 1] : 0u;
-        ce = t + 1 < nch ? cuts[t] : nsub;
+        cb = t ? cuts[t - 1] & kCutSlotMask : 0u;
+        const uint32_t cut = t + 1 < nch ? cuts[t] : nsub;
+        ce = cut & kCutSlotMask;
         const uint32_t m = ce > cb ? ce - cb : 0u;
-        cls = m <= kTinyCap ? 3u : (m <= kSmallCap ? 0u : (m <= kBigCap ? 1u : 2u));
-        if (m) slot = atomicAdd(&ccount[cls], 1u);
-        else cb = ce;
+        const uint32_t last = (cut & kCutHasLast) ? ((cut >> kCutSlotBits) & (kChunk - 1u)) + 1u : m;
+        mid = last < m && m > kMiniCap ? ce - last : ce;
+        if (m) {
+            if (m <= kSmallCap) atomicAdd(&ccount[m <= kTinyCap ? 1 : 0], 1u);
+            l0 = job_list(mid - cb);
+            s0 = atomicAdd(&jcount[l0], 1u);
+            if (mid < ce) {
+                l1 = job_list(ce - mid);
+                s1 = atomicAdd(&jcount[l1], 1u);
+            }
+        } else {
+            cb = mid = ce;
+        }
     }
     __syncthreads();
-    if (t < 4) cbase[t] = ccount[t] ? atomicAdd(t < 3 ? &L.cnt[t] : L.cnt3, ccount[t]) : 0u;
+    if (t < (uint32_t)kJobLists) jbase[t] = jcount[t] ? atomicAdd(&L.cnt[job_cnt_word(t)], jcount[t]) : 0u;
+    else if (t == 64 && ccount[0]) atomicAdd(&L.cnt[0], ccount[0]);
+    else if (t == 65 && ccount[1]) atomicAdd(&L.cnt[5], ccount[1]);
     __syncthreads();
-    if (t < nch && ce > cb) {
-        L.b[cls][cbase[cls] + slot] = o + cb;
-        L.e[cls][cbase[cls] + slot] = o + ce;
+    if (mid > cb) {
+        L.b[l0][jbase[l0] + s0] = o + cb;
+        L.e[l0][jbase[l0] + s0] = o + mid;
+    }
+    if (ce > mid) {
+        L.b[l1][jbase[l1] + s1] = o + mid;
+        L.e[l1][jbase[l1] + s1] = o + ce;
     }
     // scatter of the values only (start | preceding byte << 24): the sorters
     // rebuild the 8-byte keys from the text (rot_key8_fast), which the L2s
@@ -1386,19 +1437,20 @@ __device__ __forceinline__ uint32_t place_cb(const uint32_t* __restrict__ it, co
     return it[256 + u] + it[512 + u] + (rev ? ab[c] - 1u : 0u);
 }
 
-// by threads 0 .. 255 of a workgroup (the first wave also builds the symbol
-// map); the caller's barrier publishes the tables
+// by all TH threads of a workgroup, 256 entries whatever TH (the first wave
+// also builds the symbol map); the caller's barrier publishes the tables
+template <int TH>
 __device__ __forceinline__ void place_tabs_load(const Batch& B, uint32_t s, uint32_t mode, PlaceTabs& P, uint32_t t)
 {
     if (t < 64) {
         uint32_t nin;
         make_u2s(B, s, P.u2s_, t, &nin);
     }
-    if (t < 256) {
-        const uint32_t* it = B.itab + (size_t)s * 1024;
-        P.tq_[t] = it[t];
-        P.s0_[t] = it[768 + t];
-        P.cb_[t] = place_cb(it, B.abcnt + (size_t)s * 512, mode == kModeSortA, t);
+    const uint32_t* it = B.itab + (size_t)s * 1024;
+    for (uint32_t c = t; c < 256; c += TH) {
+        P.tq_[c] = it[c];
+        P.s0_[c] = it[768 + c];
+        P.cb_[c] = place_cb(it, B.abcnt + (size_t)s * 512, mode == kModeSortA, c);
     }
 }
 
@@ -1520,7 +1572,8 @@ __device__ __forceinline__ void chunk_load(const Batch& B, uint32_t cb, uint32_t
 // at most tcap entries): nothing after it on that path reads sa or uflag
 // anywhere else.  A workgroup's entries are in slot order and contiguous (one
 // atomic add per workgroup), which is what tie_runs_direct needs to see a run:
-// a run never leaves its bucket, hence never its chunk.  When a run is left to
+// a run never leaves its bucket, and a sort job (the [cb, ce) of a workgroup
+// here) holds whole buckets.  When a run is left to
 // the text rounds, which do read every slot, first_round sorts again without
 // PLACE.
 template <int TH, int IPT, bool PLACE>
@@ -1558,7 +1611,7 @@ __global__ __launch_bounds__(TH) void bwt_chunk_sort(Batch B, const uint32_t* __
     // (the tables are published by the barrier after the sort, below: their
     // first use is place_slot in the epilogue, and with the blocked load no
     // barrier stands ahead of the sort's own)
-    if constexpr (PLACE) place_tabs_load(B, s, mode, P, t);
+    if constexpr (PLACE) place_tabs_load<TH>(B, s, mode, P, t);
     uint64_t k[IPT];
     uint32_t v[IPT];
     chunk_load<TH, IPT, PLACE>(B, cb, m, t, k, v);
@@ -2029,7 +2082,7 @@ __global__ __launch_bounds__(256) void bwt_place_sorted(Batch B, uint32_t chunks
     if (s >= B.nstreams || (B.flags[s] & kFlagHost)) return;
     const uint32_t n = B.n[s], ns = B.nsub[s], mode = B.bwt_mode[s];
     if (base >= n) return;
-    place_tabs_load(B, s, mode, P, t);
+    place_tabs_load<256>(B, s, mode, P, t);
     cs[t] = B.itab[(size_t)s * 1024 + 256 + t];
     cl[t] = B.itab[(size_t)s * 1024 + 512 + t];
     __syncthreads();
@@ -4052,6 +4105,7 @@ thread_local void* t_hook_ctx = nullptr;
 thread_local uint64_t t_last_blocks = 0;  // bzip2 blocks the calling thread's last call produced (lfm_hip_bzip2_last_blocks)
 thread_local uint32_t t_last_place = 0;  // how its sorted rotations were placed (lfm_hip_bzip2_last_place_path)
 thread_local uint32_t t_last_bwt[12] = {};  // the path its BWT took (lfm_hip_bzip2_last_bwt_stats)
+thread_local uint32_t t_last_jobs[4] = {};  // its sort jobs per sorter capacity (lfm_hip_bzip2_last_sort_jobs)
 
 // rocPRIM temporary storage for the largest use of each primitive in a batch
 // of `count` streams (size queries only: no device work).  Carved out of the
@@ -4088,10 +4142,14 @@ size_t prim_tmp_bytes(uint32_t count, uint32_t cap)
 //   [1]    chunks of class 1 (<= kBigCap); then the length of the compacted
 //          group keys of a text round
 //   [2]    chunks of class 2 (rocPRIM segmented sort)
-//   [3]    streams whose Huffman heaps need u64 entries (rle2; Batch::wide_cnt)
-//   [4]    Huffman code-length retries (statistics only)
+//   [3]    sort jobs <= kMiniCap from the bucket pass; zeroed once the host has
+//          read them, then streams whose Huffman heaps need u64 entries (rle2;
+//          Batch::wide_cnt)
+//   [4]    sort jobs <= kTinyCap; zeroed with [3], then Huffman code-length
+//          retries (statistics only)
 //   [5]    chunks of class 3 (<= kTinyCap)
-//   [6]    unused
+//   [6]    sort jobs <= kSmallCap (the jobs <= kBigCap and the segmented
+//          ones are the chunks of classes 1 and 2: [1], [2])
 //   [7]    tied runs tie_runs_direct left to the tie rounds
 struct Scratch {
     uint64_t* offs;    // nstreams + 1 byte offsets of the compacted streams
@@ -4106,6 +4164,8 @@ struct Scratch {
 // text_rounds are those of the last attempt (the one after a restart, if any).
 struct BwtStats {
     uint32_t chunks[4] = {};      // chunks per class: <= kTinyCap, <= kSmallCap, <= kBigCap, segmented sort
+    uint32_t jobs[4] = {};        // sort jobs per sorter: <= kMiniCap, <= kTinyCap, <= kSmallCap, <= kBigCap
+                                  // (lfm_hip_bzip2_last_sort_jobs; not part of the report above)
     uint32_t first_ties = 0;      // tied slots after the chunk sorts
     uint32_t left_runs = 0;       // runs tie_runs_direct left
     uint32_t text_rounds = 0;     // text rounds run
@@ -4237,46 +4297,56 @@ struct TieRounds {
 
 uint32_t list_grid(uint32_t cnt) { return std::min<uint32_t>(4096, (cnt + 255) / 256); }
 
-// the nc chunks of class `cls`, in XCD-aware order: workgroup b runs on XCD b % 8
+// the nc sort jobs of list `list`, in XCD-aware order: workgroup b runs on XCD b % 8
 // (place: the sorts also append their tied slots to tl, at most tcap of them, and count them in W.cnt[0])
 template <int TH, int IPT>
-void chunk_sorts(const Batch& B, const ChunkLists& CL, int cls, uint32_t nc, bool place, const TieRounds& W, uint32_t* tl,
+void chunk_sorts(const Batch& B, const ChunkLists& CL, int list, uint32_t nc, bool place, const TieRounds& W, uint32_t* tl,
                  uint32_t tcap)
 {
     const uint32_t per = (nc + 7) / 8;
     if (!nc) return;
     if (place)
-        hipLaunchKernelGGL((bwt_chunk_sort<TH, IPT, true>), dim3(8 * per), dim3(TH), 0, W.st, B, CL.b[cls], CL.e[cls], nc,
+        hipLaunchKernelGGL((bwt_chunk_sort<TH, IPT, true>), dim3(8 * per), dim3(TH), 0, W.st, B, CL.b[list], CL.e[list], nc,
                            per, tl, W.cnt, tcap);
     else
-        hipLaunchKernelGGL((bwt_chunk_sort<TH, IPT, false>), dim3(8 * per), dim3(TH), 0, W.st, B, CL.b[cls], CL.e[cls], nc,
-                           per, nullptr, nullptr, 0u);
+        hipLaunchKernelGGL((bwt_chunk_sort<TH, IPT, false>), dim3(8 * per), dim3(TH), 0, W.st, B, CL.b[list], CL.e[list],
+                           nc, per, nullptr, nullptr, 0u);
 }
 
 // Round 0: the bucket pass, the chunk sorts by the 8-byte prefix (one host
-// synchronisation between them, for the chunk counts), then the tied list
-// and the runs short enough to order directly.
+// synchronisation between them, for the chunk and job counts), then the tied
+// list and the runs short enough to order directly.
 hipError_t first_round(const Batch& B, TieRounds& W)
 {
     hipStream_t st = W.st;
     const uint32_t count = B.nstreams;
     hipError_t e;
     ChunkLists CL;
-    const size_t q = W.N / 4;  // chunk lists in the cl0 / cl1 areas (at most 3 n / kChunk + 1 chunks per stream)
-    for (int c = 0; c < 4; ++c) {
+    // job lists in the cl0 / cl1 areas: a stream has at most 3 n / kChunk + 1
+    // chunks, twice as many jobs, and cap / 8 entries in each list
+    const size_t q = W.N / (2 * 4);
+    for (int c = 0; c < kJobLists; ++c) {
         CL.b[c] = B.cl0 + c * q;
         CL.e[c] = B.cl1 + c * q;
     }
     CL.cnt = W.cnt;
-    CL.cnt3 = W.cnt + 5;
-    uint32_t nch[6] = {0, 0, 0, 0, 0, 0};
+    uint32_t nch[8] = {};
     if ((e = hipMemsetAsync(W.cnt, 0, 32, st)) != hipSuccess) return e;
     hipLaunchKernelGGL(bwt_bucket<kBucketBits>, dim3(count), dim3(kBucketThreads), 0, st, B, CL);
-    if ((e = hipGetLastError()) != hipSuccess || (e = W.read_count(nch, 24)) != hipSuccess) return e;
+    if ((e = hipGetLastError()) != hipSuccess || (e = W.read_count(nch, 32)) != hipSuccess) return e;
+    // Words 0 to 4 have been read: zero again.  [0] becomes the tied list's
+    // length, [3] and [4] (job counts here) are the Huffman stage's counters.
+    if ((e = hipMemsetAsync(W.cnt, 0, 20, st)) != hipSuccess) return e;
     W.stats.chunks[0] = nch[5];
     W.stats.chunks[1] = nch[0];
     W.stats.chunks[2] = nch[1];
     W.stats.chunks[3] = nch[2];
+    const uint32_t jobs[kJobLists] = {nch[job_cnt_word(0)], nch[job_cnt_word(1)], nch[job_cnt_word(2)],
+                                      nch[job_cnt_word(3)], nch[job_cnt_word(4)]};
+    W.stats.jobs[0] = jobs[4];
+    W.stats.jobs[1] = jobs[3];
+    W.stats.jobs[2] = jobs[0];
+    W.stats.jobs[3] = jobs[1];
     W.stats.first_ties = W.stats.left_runs = W.stats.text_rounds = 0;
     // The sorts place their rotations themselves (PLACE) when the batch is
     // induced and every chunk goes through them: the segmented sort's keys
@@ -4289,20 +4359,19 @@ hipError_t first_round(const Batch& B, TieRounds& W)
     W.stats.fused_sorts = fused;
     W.first_read = false;
     auto sorts = [&](bool place, uint32_t* tl) {
-        chunk_sorts<kTinyCap / kCsItems, kCsItems>(B, CL, 3, nch[5], place, W, tl, (uint32_t)W.N);
-        chunk_sorts<kCsThreads, kCsItems>(B, CL, 0, nch[0], place, W, tl, (uint32_t)W.N);
-        chunk_sorts<kBigThreads, kBigItems>(B, CL, 1, nch[1], place, W, tl, (uint32_t)W.N);
+        chunk_sorts<kMiniCap / kCsItems, kCsItems>(B, CL, 4, jobs[4], place, W, tl, (uint32_t)W.N);
+        chunk_sorts<kTinyCap / kCsItems, kCsItems>(B, CL, 3, jobs[3], place, W, tl, (uint32_t)W.N);
+        chunk_sorts<kCsThreads, kCsItems>(B, CL, 0, jobs[0], place, W, tl, (uint32_t)W.N);
+        chunk_sorts<kBigThreads, kBigItems>(B, CL, 1, jobs[1], place, W, tl, (uint32_t)W.N);
     };
     W.covered = kKeyBytes;
     W.none_left = false;
     if (fused) {
         // The placing sorts list their tied slots themselves, in the vals_b
-        // area (N entries; the text rounds' and free here: the chunk lists in
-        // cl0 / cl1 are still being read), and write sa at those slots only.
-        // cnt[0] held the chunk count of class 0; from here on it is the
-        // list's length.
+        // area (N entries; the text rounds' and free here: the job lists in
+        // cl0 / cl1 are still being read), and write sa at those slots only;
+        // cnt[0] is the list's length.
         uint32_t* tl = B.vals_b;
-        if ((e = hipMemsetAsync(W.cnt, 0, 4, st)) != hipSuccess) return e;
         sorts(true, tl);
         hipLaunchKernelGGL(tie_runs_direct, dim3(1024), dim3(256), 0, st, B, tl, W.cnt, W.cnt + 7);
         // queued ahead of the host's read of the counts; void if a run was left (place_path)
@@ -4316,7 +4385,7 @@ hipError_t first_round(const Batch& B, TieRounds& W)
             return hipSuccess;
         }
         // A run was left to the text rounds, which read sa and uflag at every
-        // slot: the sorts once more without PLACE, from vals_a and the chunk
+        // slot: the sorts once more without PLACE, from vals_a and the job
         // lists (both intact), then the tied list as on the unfused path.
         if ((e = hipMemsetAsync(W.cnt + 7, 0, 4, st)) != hipSuccess) return e;
     }
@@ -4584,6 +4653,7 @@ int bzip2_blocks(const void* d_img, const uint32_t dims[5], const uint32_t bs[5]
                                 bwt_stats.first_ties, bwt_stats.left_runs, bwt_stats.text_rounds, bwt_stats.restarted,
                                 bwt_stats.rank_form, bwt_stats.doubling_rounds, bwt_stats.flag_periodic, 0u};
         std::copy(v, v + 12, t_last_bwt);
+        std::copy(bwt_stats.jobs, bwt_stats.jobs + 4, t_last_jobs);
     }
     if (!B.it_full) {
         // the other type placed by one scan, which writes the symbols ll[]
@@ -4716,6 +4786,11 @@ extern "C" uint64_t lfm_hip_bzip2_last_blocks(void) { return t_last_blocks; }
 extern "C" void lfm_hip_bzip2_last_bwt_stats(uint32_t out[12])
 {
     if (out) std::copy(t_last_bwt, t_last_bwt + 12, out);
+}
+
+extern "C" void lfm_hip_bzip2_last_sort_jobs(uint32_t out[4])
+{
+    if (out) std::copy(t_last_jobs, t_last_jobs + 4, out);
 }
 
 extern "C" uint32_t lfm_hip_bzip2_last_place_path(void) { return t_last_place; }

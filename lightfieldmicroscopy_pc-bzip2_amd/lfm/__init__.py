@@ -55,7 +55,7 @@ EXPORTS = [
     "lfm_hip_bzip2_blocks", "lfm_hip_bzip2_last_stage_ms", "lfm_hip_bunzip2_workspace_bytes", "lfm_hip_bunzip2_blocks", "lfm_hip_scatter_blocks",
     "lfm_hip_crop_region", "lfm_hip_bzip2_workspace_bytes_multi", "lfm_hip_bzip2_max_count_multi",
     "lfm_hip_bzip2_blocks_multi", "lfm_hip_bzip2_last_blocks", "lfm_hip_bzip2_last_bwt_stats",
-    "lfm_hip_bzip2_last_place_path",
+    "lfm_hip_bzip2_last_place_path", "lfm_hip_bzip2_last_sort_jobs",
     "lfm_hip_bunzip2_max_parts", "lfm_hip_bunzip2_workspace_bytes_multi", "lfm_hip_bunzip2_blocks_multi",
     "lfm_hip_bunzip2_issue_multi", "lfm_hip_bunzip2_set_periodic", "lfm_hip_bunzip2_get_periodic",
 ]
@@ -224,6 +224,8 @@ def lib():
     L.lfm_hip_bzip2_last_blocks.restype = ctypes.c_uint64
     L.lfm_hip_bzip2_last_bwt_stats.argtypes = [u32p]
     L.lfm_hip_bzip2_last_bwt_stats.restype = None
+    L.lfm_hip_bzip2_last_sort_jobs.argtypes = [u32p]
+    L.lfm_hip_bzip2_last_sort_jobs.restype = None
     L.lfm_hip_bzip2_last_place_path.argtypes = []
     L.lfm_hip_bzip2_last_place_path.restype = ctypes.c_uint32
     L.lfm_set_bzip2_multiblock.argtypes = [ctypes.c_int]
@@ -1312,6 +1314,18 @@ def bzip2_last_bwt_stats():
     out = (ctypes.c_uint32 * 12)()
     lib().lfm_hip_bzip2_last_bwt_stats(out)
     return dict(zip(BWT_STATS, list(out)))
+
+
+SORT_JOB_CAPS = (512, 1024, 2048, 4096)
+
+
+def bzip2_last_sort_jobs():
+    """The sort jobs of this thread's last bzip2_device call per sorter
+    capacity (lfm_hip_bzip2_last_sort_jobs, lfm_hip.h), as a dict over
+    SORT_JOB_CAPS."""
+    out = (ctypes.c_uint32 * 4)()
+    lib().lfm_hip_bzip2_last_sort_jobs(out)
+    return dict(zip(SORT_JOB_CAPS, list(out)))
 
 
 def bzip2_last_place_path():
