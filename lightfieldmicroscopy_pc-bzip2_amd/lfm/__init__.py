@@ -1173,6 +1173,30 @@ def crop_device(d_src, src_dims, lb, n, bpp, d_dst, stream=None):
            "lfm_hip_crop_region")
 
 
+def scatter_blocks_device(d_blocks, stride, first, count, dims, bs, bpp, d_img, stream=None):
+    """lfm_hip_scatter_blocks: blocks first .. first + count - 1 of the x-fastest
+    block grid (dims, bs: [x, y, z, c, t]; bpp bytes per sample), block first + i
+    at d_blocks + i * stride with its bytes x fastest, then y, z, c, t, into the
+    device image d_img (tensors or raw pointers); asynchronous on `stream`.
+    The block range, the stride and the extents are checked here: the library
+    launches whatever it is given."""
+    fn = _need("lfm_hip_scatter_blocks")
+    p = lambda t: t.data_ptr() if hasattr(t, "data_ptr") else int(t)  # noqa: E731
+    if len(dims) != 5 or len(bs) != 5:
+        raise ValueError("scatter_blocks_device: dims and bs have five entries")
+    if any(int(v) < 1 or int(v) >= 1 << 32 for v in list(dims) + list(bs) + [bpp]):
+        raise ValueError("scatter_blocks_device: extents are 32-bit unsigned and not 0")
+    total = int(np.prod([-(-int(d) // int(b)) for d, b in zip(dims, bs)], dtype=np.uint64))
+    if int(first) < 0 or int(count) < 1 or int(first) + int(count) > total:
+        raise ValueError("scatter_blocks_device: blocks %d .. %d of a grid of %d"
+                         % (first, int(first) + int(count) - 1, total))
+    block_bytes = int(np.prod([min(int(d), int(b)) for d, b in zip(dims, bs)], dtype=np.uint64)) * int(bpp)
+    if not block_bytes <= int(stride) < 1 << 32:
+        raise ValueError("scatter_blocks_device: stride %d, a block holds up to %d bytes" % (stride, block_bytes))
+    _check(fn(p(d_blocks), int(stride), int(first), int(count), _u32(dims), _u32(bs), int(bpp), p(d_img),
+              _stream(stream)), "lfm_hip_scatter_blocks")
+
+
 def predict_device(d_in, d_out, W, H, nframes, T, family, predictor, video=0, z0=0, d_prev=None, stream=None):
     """Launch the fused predictor + symbolize kernel on device tensors (or raw pointers)."""
     p = lambda t: None if t is None else (t.data_ptr() if hasattr(t, "data_ptr") else int(t))  # noqa: E731
