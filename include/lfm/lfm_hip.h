@@ -39,9 +39,66 @@ enum lfm_hip_status {
  * d_in holds frames z0 .. z0+nframes-1 (W*H uint16 each, x fastest); frame
  * z is temporal when (video_bit & z) is odd, and then uses the raw frame z-1
  * (d_in of the previous frame, or d_prev for the first one).  predictor 0
- * copies the raw frames.  d_out receives uint16 symbols in the same layout. */
+ * copies the raw frames.  d_out receives uint16 symbols in the same layout.
+ * Alignment: any 2-byte aligned pointers are legal.  The ring, vec and
+ * frame-pair kernels move 16 bytes per lane between d_in / d_prev / d_out and
+ * LDS, so they run only when d_in, d_out and (where frame 0 is temporal: video
+ * bit and odd z0) d_prev are 16-byte aligned; with any other base the call
+ * takes predict_generic, which makes 2-byte accesses only and is several times
+ * slower.  lfm_hip_predict_candidates follows the same rule for d_frame and
+ * d_out7 and then runs one generic launch per predictor. */
 int lfm_hip_predict(const uint16_t* d_in, const uint16_t* d_prev, uint16_t* d_out, int W, int H, int nframes,
                     int T, int family, int predictor, int video_bit, int z0, void* stream);
+
+/* One kernel launch of a forward-predictor call, as lfm_hip_predict_plan reports it. */
+enum lfm_predict_kernel {
+    LFM_PK_COPY = 0,      /* predictor 0: a device-to-device copy, no kernel */
+    LFM_PK_GENERIC = 1,   /* predict_generic: one thread per pixel            */
+    LFM_PK_RING = 2,      /* predict_ring: T <= 31, W % 8 == 0, W >= 32       */
+    LFM_PK_VEC = 3,       /* predict_vec: T 13 / 15                           */
+    LFM_PK_VEC_PAIR = 4,  /* predict_vec_pair: video volumes, T 13 / 15       */
+    LFM_PK_CANDS = 5      /* predict_cands: seven candidates, grid_y = 7      */
+};
+typedef struct lfm_predict_launch {
+    int kernel;         /* enum lfm_predict_kernel */
+    int first;          /* first frame of the call that this launch codes */
+    int nframes;        /* frames it codes (vec_pair: 2 * pairs) */
+    int pairs;          /* vec_pair: (spatial, temporal) frame pairs, else 0 */
+    int strip;          /* pixels per strip (0: copy / generic, as all fields to xcd_map) */
+    int nstrip;         /* strips per row, the last one may be partial */
+    int rows_per_step;  /* rows (of each frame) a workgroup codes between two barriers */
+    int rows_per_piece; /* rows per row piece, a whole number of steps */
+    int npiece;         /* row pieces per frame */
+    int R;              /* row slots of the LDS ring */
+    int RP;             /* row slots of the previous-frame ring (temporal frames), else 0 */
+    int halo;           /* pixels left of a strip kept per ring slot: 16 or 32 */
+    int xcd_map;        /* 1: the strips of a (frame, piece) are workgroups b, b + 8, ... */
+    int grid_x, grid_y; /* workgroups */
+    int threads;        /* per workgroup */
+    int lds_bytes;      /* dynamic LDS per workgroup */
+} lfm_predict_launch;
+#define LFM_PREDICT_MAX_LAUNCHES 7
+
+/* The launches lfm_hip_predict would make for these arguments, or with
+ * `candidates` lfm_hip_predict_candidates for one W x H frame (nframes,
+ * predictor, video_bit and z0 are then ignored), in launch order, without
+ * launching anything: at most three (a video volume's temporal first frame,
+ * its frame pairs, its unpaired last frame), and seven for the candidates'
+ * per-predictor generic loop.  `aligned` says whether the call's pointers are
+ * 16-byte aligned (see lfm_hip_predict).  Both entries launch exactly this
+ * list.  Returns the number of launches written to out[0 .. cap), or -1 for
+ * arguments lfm_hip_predict refuses or a cap that is too small.  With the
+ * automatic piece count it asks the HIP runtime for the kernel's occupancy and
+ * the device's CU count (256 CUs x 1 workgroup without a device); with a
+ * forced piece count (below) it is pure: no HIP call. */
+int lfm_hip_predict_plan(int W, int H, int nframes, int T, int family, int predictor, int video_bit, int z0,
+                         int candidates, int aligned, lfm_predict_launch* out, int cap);
+/* Test hook, process-wide: n > 0 replaces the planner's "resident workgroups /
+ * (frames x strips)" piece count by n, for every later plan of every thread;
+ * the cap of H / (2 (T + 1)) pieces and the rounding of a piece to whole steps
+ * still apply.  0 (the default) restores the automatic count.  Returns the
+ * previous value.  Production code never calls it. */
+int lfm_hip_predict_set_pieces(int n);
 
 /* Inverse of lfm_hip_predict (decode): symbols -> pixels for nframes frames
  * starting at global frame z0; a temporal first frame (video, odd z0) needs

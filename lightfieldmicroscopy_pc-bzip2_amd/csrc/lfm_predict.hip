@@ -31,6 +31,7 @@
 // written per pixel, +2 B read on temporal frames.
 #include <hip/hip_runtime.h>
 #include <cstdint>
+#include <atomic>
 #include <cstdlib>
 #include "lfm_cases.h"
 #include "lfm_hip.h"
@@ -1163,11 +1164,15 @@ struct Plan {
     size_t lds;
 };
 
+// lfm_hip_predict_set_pieces: 0 = automatic, n > 0 replaces the occupancy term below
+static std::atomic<int> g_force_pieces{0};
+
 // Split each frame into npiece row pieces so that the items (copies x frames
 // x pieces x strips) fill the resident workgroup slots about once: a piece
 // re-reads only its T+1 priming rows, so fewer, taller pieces waste less
 // (1.5 % at 2048 rows / 3 pieces vs 6 % for 256-row segments).  Pieces stay
-// >= 2(T+1) rows.
+// >= 2(T+1) rows.  With a forced piece count (a test hook) the count replaces
+// resident / cols and no HIP call is made.
 // rs = rows per step, sw = strip width (pixels), halo = left halo pixels per slot
 // rings = haloed row rings per workgroup (2 for the frame-pair kernel)
 static hipError_t make_plan_shape(const FrameSet& p, const void* fn, int threads, int rs, int pd, int sw, int halo,
@@ -1180,16 +1185,19 @@ static hipError_t make_plan_shape(const FrameSet& p, const void* fn, int threads
     pl.lds = ((size_t)rings * pl.R * (pl.halo + sw) + (size_t)pl.RP * sw) * sizeof(uint16_t);
     pl.nstrip = (p.W + sw - 1) / sw;
     const int ncw = rs;  // rows are padded to whole steps below
-    int occ = 0;
-    hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, fn, threads, pl.lds);
-    if (e != hipSuccess || occ <= 0) occ = 1;
-    int dev = 0, ncu = 0;
-    (void)hipGetDevice(&dev);
-    (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
-    if (ncu <= 0) ncu = 256;
-    const int resident = occ * ncu;
-    const int cols = copies * p.nz * pl.nstrip;
-    int npiece = std::max(1, resident / std::max(1, cols));
+    int npiece = g_force_pieces.load(std::memory_order_relaxed);
+    if (npiece <= 0) {
+        int occ = 0;
+        hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, fn, threads, pl.lds);
+        if (e != hipSuccess || occ <= 0) occ = 1;
+        int dev = 0, ncu = 0;
+        (void)hipGetDevice(&dev);
+        (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
+        if (ncu <= 0) ncu = 256;
+        const int resident = occ * ncu;
+        const int cols = copies * p.nz * pl.nstrip;
+        npiece = std::max(1, resident / std::max(1, cols));
+    }
     npiece = std::min(npiece, std::max(1, p.H / (2 * (p.T + 1))));
     int rows = (p.H + npiece - 1) / npiece;
     rows = (rows + ncw - 1) / ncw * ncw;
@@ -1221,6 +1229,76 @@ static bool fast_ok(const FrameSet& p, int force_generic)
     return !force_generic && p.T <= kMaxFastT && (p.W % 8) == 0 && p.W >= 32;
 }
 
+// ---- decide, then launch.  A call's launches are decided first, as a list of
+// records (at most three: a video volume's temporal first frame, its frame
+// pairs, its unpaired last frame; seven for the candidates' per-predictor
+// loop), and run_launches starts exactly that list.  lfm_hip_predict_plan
+// returns the records' public part without launching.
+struct Launch {
+    lfm_predict_launch d;
+    const void* fn;  // the kernel (null: copy)
+    size_t lds;      // dynamic LDS bytes
+    int out_frame;   // d_out frame this launch starts writing at (d.first, but k - 1 in the candidates' loop)
+};
+
+struct LaunchList {
+    int n = 0;
+    Launch l[LFM_PREDICT_MAX_LAUNCHES];
+    Launch& add()
+    {
+        Launch& L = l[n++];
+        L = Launch{};
+        return L;
+    }
+};
+
+// frames first .. first + n - 1 of p as a volume of their own (planning view:
+// pointers are not touched)
+static FrameSet sub_volume(const FrameSet& p, int first, int n)
+{
+    FrameSet q = p;
+    q.nz = n;
+    q.z0 = p.z0 + first;
+    return q;
+}
+
+static void fill_ring_launch(Launch& L, int kernel, const void* fn, int threads, int first, int nframes, int pairs,
+                             int sw, int rs, const Plan& pl, int gy)
+{
+    L.d.kernel = kernel;
+    L.d.first = first;
+    L.d.nframes = nframes;
+    L.d.pairs = pairs;
+    L.d.strip = sw;
+    L.d.nstrip = pl.nstrip;
+    L.d.rows_per_step = rs;
+    L.d.rows_per_piece = pl.rows_per_piece;
+    L.d.npiece = pl.npiece;
+    L.d.R = pl.R;
+    L.d.RP = pl.RP;
+    L.d.halo = pl.halo;
+    L.d.xcd_map = pl.xcd_map;
+    L.d.grid_x = pl.grid;
+    L.d.grid_y = gy;
+    L.d.threads = threads;
+    L.d.lds_bytes = (int)pl.lds;
+    L.fn = fn;
+    L.lds = pl.lds;
+    L.out_frame = first;
+}
+
+static void fill_generic_launch(Launch& L, const void* fn, const FrameSet& p, int out_frame)
+{
+    const size_t total = (size_t)p.W * p.H * p.nz;
+    L.d.kernel = LFM_PK_GENERIC;
+    L.d.nframes = p.nz;
+    L.d.grid_x = (int)std::min<size_t>((total + 255) / 256, 256 * 16);
+    L.d.grid_y = 1;
+    L.d.threads = 256;
+    L.fn = fn;
+    L.out_frame = out_frame;
+}
+
 // vectorised path shape per family (WPR waves per row = strip of WPR * 512
 // pixels, NCW compute waves, RPW rows per compute wave and step, PD steps of
 // prefetch).  Measured on config 3 (scripts/pred_probe.hip, profiles/r03_pred_probe*.jsonl):
@@ -1245,14 +1323,17 @@ struct VecShape {
     static constexpr int PD = FAM == 0 ? 3 : LFM_VEC_PD;
 };
 
+// frames first .. first + n - 1 of p in one predict_vec launch
 template <int FAM, int K, int T, int WPR, int NCW, int RPW, int PD>
-static hipError_t launch_vec_shape(const FrameSet& p, hipStream_t st)
+static hipError_t plan_vec_shape(const FrameSet& p, int first, int n, Launch& L)
 {
     const void* fn = (const void*)predict_vec<FAM, K, T, WPR, NCW, RPW, PD>;
     Plan pl;
-    hipError_t e = make_plan_shape(p, fn, NCW * 64 + 64, (NCW / WPR) * RPW, PD, WPR * 512, kVHalo, 1, pl);
+    hipError_t e = make_plan_shape(sub_volume(p, first, n), fn, NCW * 64 + 64, (NCW / WPR) * RPW, PD, WPR * 512, kVHalo,
+                                   1, pl);
     if (e != hipSuccess) return e;
-    return launch_plan(fn, p, pl, NCW, 1, st);
+    fill_ring_launch(L, LFM_PK_VEC, fn, NCW * 64 + 64, first, n, 0, WPR * 512, (NCW / WPR) * RPW, pl, 1);
+    return hipSuccess;
 }
 
 // frame-pair shape (video volumes): NCW compute waves, NCW / 2 per frame
@@ -1268,23 +1349,13 @@ struct PairShape {
 // launch; a temporal frame 0 (z0 odd: its previous frame is p.prev) and an
 // unpaired last spatial frame go through predict_vec on their own.
 template <int FAM, int K, int T, int WPR, int NCW, int RPW, int PD>
-static hipError_t launch_vec_pairs(const FrameSet& p, hipStream_t st)
+static hipError_t plan_vec_pairs(const FrameSet& p, LaunchList& ll)
 {
-    const size_t fs = (size_t)p.W * p.H;
     const int first = (p.z0 & 1) ? 1 : 0;
     const int npairs = (p.nz - first) / 2;
     using S = VecShape<FAM>;
-    auto single = [&](int fz) -> hipError_t {
-        FrameSet q = p;
-        q.in = p.in + (size_t)fz * fs;
-        q.out = p.out + (size_t)fz * fs;
-        q.prev = fz ? p.in + (size_t)(fz - 1) * fs : p.prev;
-        q.nz = 1;
-        q.z0 = p.z0 + fz;
-        return launch_vec_shape<FAM, K, T, S::WPR, S::NCW, S::RPW, S::PD>(q, st);
-    };
     if (first) {
-        if (hipError_t e = single(0)) return e;
+        if (hipError_t e = plan_vec_shape<FAM, K, T, S::WPR, S::NCW, S::RPW, S::PD>(p, 0, 1, ll.add())) return e;
     }
     if (npairs > 0) {
         const void* fn = (const void*)predict_vec_pair<FAM, K, T, WPR, NCW, RPW, PD>;
@@ -1294,32 +1365,27 @@ static hipError_t launch_vec_pairs(const FrameSet& p, hipStream_t st)
         Plan pl;
         hipError_t e = make_plan_shape(q, fn, NCW * 64 + 64, (NCW / 2 / WPR) * RPW, PD, WPR * 512, kVHalo, 1, pl, 2);
         if (e != hipSuccess) return e;
-        FrameSet a = p;
-        a.halo = pl.halo;
-        int a_rows = pl.rows_per_piece, a_np = pl.npiece, a_nstrip = pl.nstrip, a_x = pl.xcd_map, a_R = pl.R,
-            a_first = first;
-        void* args[] = {(void*)&a, (void*)&a_rows, (void*)&a_np, (void*)&a_nstrip, (void*)&a_x, (void*)&a_R,
-                        (void*)&a_first};
-        e = hipLaunchKernel(fn, dim3(pl.grid), dim3(NCW * 64 + 64), args, pl.lds, st);
-        if (e != hipSuccess) return e;
-        if ((e = hipGetLastError()) != hipSuccess) return e;
+        fill_ring_launch(ll.add(), LFM_PK_VEC_PAIR, fn, NCW * 64 + 64, first, 2 * npairs, npairs, WPR * 512,
+                         (NCW / 2 / WPR) * RPW, pl, 1);
     }
-    if (first + 2 * npairs < p.nz) return single(p.nz - 1);
+    if (first + 2 * npairs < p.nz)
+        return plan_vec_shape<FAM, K, T, S::WPR, S::NCW, S::RPW, S::PD>(p, p.nz - 1, 1, ll.add());
     return hipSuccess;
 }
 
-template <int FAM, int K>
-static hipError_t launch_vec(const FrameSet& p, hipStream_t st)
+template <int FAM, int K, int T>
+static hipError_t plan_vec_t(const FrameSet& p, LaunchList& ll)
 {
     using S = VecShape<FAM>;
     using PS = PairShape<FAM>;
-    const bool pairs = p.video && p.nz >= 2;
-    if (p.T == 15) {
-        if (pairs) return launch_vec_pairs<FAM, K, 15, PS::WPR, PS::NCW, PS::RPW, PS::PD>(p, st);
-        return launch_vec_shape<FAM, K, 15, S::WPR, S::NCW, S::RPW, S::PD>(p, st);
-    }
-    if (pairs) return launch_vec_pairs<FAM, K, 13, PS::WPR, PS::NCW, PS::RPW, PS::PD>(p, st);
-    return launch_vec_shape<FAM, K, 13, S::WPR, S::NCW, S::RPW, S::PD>(p, st);
+    if (p.video && p.nz >= 2) return plan_vec_pairs<FAM, K, T, PS::WPR, PS::NCW, PS::RPW, PS::PD>(p, ll);
+    return plan_vec_shape<FAM, K, T, S::WPR, S::NCW, S::RPW, S::PD>(p, 0, p.nz, ll.add());
+}
+
+template <int FAM, int K>
+static hipError_t plan_vec(const FrameSet& p, LaunchList& ll)
+{
+    return p.T == 15 ? plan_vec_t<FAM, K, 15>(p, ll) : plan_vec_t<FAM, K, 13>(p, ll);
 }
 
 static bool vec_ok(const FrameSet& p, int force_generic)
@@ -1327,48 +1393,149 @@ static bool vec_ok(const FrameSet& p, int force_generic)
     return !force_generic && (p.T == 13 || p.T == 15) && (p.W % 8) == 0 && p.W >= 32;
 }
 
+// the launches of lfm_hip_predict for one (family, predictor >= 1)
 template <int FAM, int K>
-static hipError_t launch_k(const FrameSet& p, hipStream_t st, int force_generic)
+static hipError_t plan_k(const FrameSet& p, int force_generic, LaunchList& ll)
 {
-    if (vec_ok(p, force_generic)) return launch_vec<FAM, K>(p, st);
+    if (vec_ok(p, force_generic)) return plan_vec<FAM, K>(p, ll);
     if (!fast_ok(p, force_generic)) {
-        size_t total = (size_t)p.W * p.H * p.nz;
-        int grid = (int)std::min<size_t>((total + 255) / 256, 256 * 16);
-        hipLaunchKernelGGL((predict_generic<FAM, K>), dim3(grid), dim3(256), 0, st, p);
-        return hipGetLastError();
+        fill_generic_launch(ll.add(), (const void*)predict_generic<FAM, K>, p, 0);
+        return hipSuccess;
     }
     using RS = RingShape<FAM>;
     const void* fn = (const void*)predict_ring<FAM, K, RS::NCW, RS::RPW, RS::PD>;
     Plan pl;
     hipError_t e = make_plan(p, fn, RS::NCW, RS::RPW, RS::PD, 1, pl);
     if (e != hipSuccess) return e;
-    return launch_plan(fn, p, pl, RS::NCW, 1, st);
+    fill_ring_launch(ll.add(), LFM_PK_RING, fn, RS::NCW * 64 + 64, 0, p.nz, 0, kStrip, RS::NCW * RS::RPW, pl, 1);
+    return hipSuccess;
 }
 
+// the launches of lfm_hip_predict_candidates: the seven-candidate kernel, or
+// where the ring does not apply one generic launch per predictor
 template <int FAM>
-static hipError_t launch_cands(const FrameSet& p, hipStream_t st)
+static hipError_t plan_cands(const FrameSet& p, int force_generic, LaunchList& ll)
 {
+    if (!fast_ok(p, force_generic)) {
+        fill_generic_launch(ll.add(), (const void*)predict_generic<FAM, 1>, p, 0);
+        fill_generic_launch(ll.add(), (const void*)predict_generic<FAM, 2>, p, 1);
+        fill_generic_launch(ll.add(), (const void*)predict_generic<FAM, 3>, p, 2);
+        fill_generic_launch(ll.add(), (const void*)predict_generic<FAM, 4>, p, 3);
+        fill_generic_launch(ll.add(), (const void*)predict_generic<FAM, 5>, p, 4);
+        fill_generic_launch(ll.add(), (const void*)predict_generic<FAM, 6>, p, 5);
+        fill_generic_launch(ll.add(), (const void*)predict_generic<FAM, 7>, p, 6);
+        return hipSuccess;
+    }
     using RS = RingShape<FAM>;
     const void* fn = (const void*)predict_cands<FAM, RS::NCW, RS::RPW, RS::PD>;
     Plan pl;
     hipError_t e = make_plan(p, fn, RS::NCW, RS::RPW, RS::PD, 7, pl);
     if (e != hipSuccess) return e;
-    return launch_plan(fn, p, pl, RS::NCW, 7, st);
+    fill_ring_launch(ll.add(), LFM_PK_CANDS, fn, RS::NCW * 64 + 64, 0, 1, 0, kStrip, RS::NCW * RS::RPW, pl, 7);
+    return hipSuccess;
 }
 
 template <int FAM>
-static hipError_t launch_fam(int k, const FrameSet& p, hipStream_t st, int force_generic)
+static hipError_t plan_fam(int k, const FrameSet& p, int force_generic, LaunchList& ll)
 {
     switch (k) {
-    case 1: return launch_k<FAM, 1>(p, st, force_generic);
-    case 2: return launch_k<FAM, 2>(p, st, force_generic);
-    case 3: return launch_k<FAM, 3>(p, st, force_generic);
-    case 4: return launch_k<FAM, 4>(p, st, force_generic);
-    case 5: return launch_k<FAM, 5>(p, st, force_generic);
-    case 6: return launch_k<FAM, 6>(p, st, force_generic);
-    case 7: return launch_k<FAM, 7>(p, st, force_generic);
+    case 1: return plan_k<FAM, 1>(p, force_generic, ll);
+    case 2: return plan_k<FAM, 2>(p, force_generic, ll);
+    case 3: return plan_k<FAM, 3>(p, force_generic, ll);
+    case 4: return plan_k<FAM, 4>(p, force_generic, ll);
+    case 5: return plan_k<FAM, 5>(p, force_generic, ll);
+    case 6: return plan_k<FAM, 6>(p, force_generic, ll);
+    case 7: return plan_k<FAM, 7>(p, force_generic, ll);
     }
     return hipErrorInvalidValue;
+}
+
+// The one decision of a call: predictor 0 is a copy, `cands` the candidates
+// entry.  aligned16: d_in, d_out and (where frame 0 is temporal) d_prev are
+// 16-byte aligned; the ring, vec and pair kernels move 16 bytes per lane
+// between those pointers and LDS, so any other base takes predict_generic.
+static hipError_t plan_call(const FrameSet& p, int family, int predictor, bool cands, bool aligned16, LaunchList& ll)
+{
+    ll.n = 0;
+    if (!cands && predictor == 0) {  // candidate 0: the raw frames (klb_imageIO.cpp:1690, :1258)
+        Launch& L = ll.add();
+        L.d.kernel = LFM_PK_COPY;
+        L.d.nframes = p.nz;
+        return hipSuccess;
+    }
+    const int force_generic = lfm_hip_force_generic() || !aligned16;
+    switch (family) {
+    case 0: return cands ? plan_cands<0>(p, force_generic, ll) : plan_fam<0>(predictor, p, force_generic, ll);
+    case 1: return cands ? plan_cands<1>(p, force_generic, ll) : plan_fam<1>(predictor, p, force_generic, ll);
+    case 2: return cands ? plan_cands<2>(p, force_generic, ll) : plan_fam<2>(predictor, p, force_generic, ll);
+    }
+    return hipErrorInvalidValue;
+}
+
+static hipError_t run_launch(const Launch& L, const FrameSet& p, hipStream_t st)
+{
+    const lfm_predict_launch& d = L.d;
+    const size_t fs = (size_t)p.W * p.H;
+    if (d.kernel == LFM_PK_COPY) {
+        return hipMemcpyAsync(p.out, p.in, fs * p.nz * sizeof(uint16_t), hipMemcpyDeviceToDevice, st);
+    }
+    hipError_t e;
+    if (d.kernel == LFM_PK_VEC_PAIR) {  // the kernel finds its pairs in the whole volume
+        FrameSet a = p;
+        a.halo = d.halo;
+        int a_rows = d.rows_per_piece, a_np = d.npiece, a_nstrip = d.nstrip, a_x = d.xcd_map, a_R = d.R,
+            a_first = d.first;
+        void* args[] = {(void*)&a, (void*)&a_rows, (void*)&a_np, (void*)&a_nstrip, (void*)&a_x, (void*)&a_R,
+                        (void*)&a_first};
+        e = hipLaunchKernel(L.fn, dim3(d.grid_x), dim3(d.threads), args, L.lds, st);
+        if (e != hipSuccess) return e;
+        return hipGetLastError();
+    }
+    FrameSet q = sub_volume(p, d.first, d.nframes);
+    q.in = p.in + (size_t)d.first * fs;
+    q.prev = d.first ? p.in + (size_t)(d.first - 1) * fs : p.prev;
+    q.out = p.out + (size_t)L.out_frame * fs;
+    if (d.kernel == LFM_PK_GENERIC) {
+        void* args[] = {(void*)&q};
+        e = hipLaunchKernel(L.fn, dim3(d.grid_x), dim3(d.threads), args, 0, st);
+        if (e != hipSuccess) return e;
+        return hipGetLastError();
+    }
+    const Plan pl{d.R, d.RP, d.halo, d.rows_per_piece, d.npiece, d.nstrip, d.xcd_map, d.grid_x, L.lds};
+    return launch_plan(L.fn, q, pl, d.threads / 64 - 1, d.grid_y, st);
+}
+
+static hipError_t run_launches(const LaunchList& ll, const FrameSet& p, hipStream_t st)
+{
+    for (int i = 0; i < ll.n; ++i) {
+        if (hipError_t e = run_launch(ll.l[i], p, st)) return e;
+    }
+    return hipSuccess;
+}
+
+// The probes (scripts/*_probe.hip) time single shapes through these.
+template <int FAM, int K, int T, int WPR, int NCW, int RPW, int PD>
+static hipError_t launch_vec_shape(const FrameSet& p, hipStream_t st)
+{
+    LaunchList ll;
+    if (hipError_t e = plan_vec_shape<FAM, K, T, WPR, NCW, RPW, PD>(p, 0, p.nz, ll.add())) return e;
+    return run_launches(ll, p, st);
+}
+
+template <int FAM, int K, int T, int WPR, int NCW, int RPW, int PD>
+static hipError_t launch_vec_pairs(const FrameSet& p, hipStream_t st)
+{
+    LaunchList ll;
+    if (hipError_t e = plan_vec_pairs<FAM, K, T, WPR, NCW, RPW, PD>(p, ll)) return e;
+    return run_launches(ll, p, st);
+}
+
+template <int FAM, int K>
+static hipError_t launch_vec(const FrameSet& p, hipStream_t st)
+{
+    LaunchList ll;
+    if (hipError_t e = plan_vec<FAM, K>(p, ll)) return e;
+    return run_launches(ll, p, st);
 }
 
 } // namespace lfm
@@ -1377,6 +1544,8 @@ static hipError_t launch_fam(int k, const FrameSet& p, hipStream_t st, int force
 // launchers only: LFM_PREDICT_NO_ENTRY drops the C entry points below, which
 // instantiate every kernel
 #ifndef LFM_PREDICT_NO_ENTRY
+static bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
+
 extern "C" int lfm_hip_predict(const uint16_t* d_in, const uint16_t* d_prev, uint16_t* d_out, int W, int H,
                                int nframes, int T, int family, int predictor, int video_bit, int z0,
                                void* stream_)
@@ -1384,20 +1553,13 @@ extern "C" int lfm_hip_predict(const uint16_t* d_in, const uint16_t* d_prev, uin
     hipStream_t stream = (hipStream_t)stream_;
     if (W <= 0 || H <= 0 || nframes <= 0 || T <= 0 || predictor < 0 || predictor > 7 || family < 0 || family > 2)
         return LFM_HIP_EINVAL;
-    const size_t bytes = (size_t)W * H * nframes * sizeof(uint16_t);
-    if (predictor == 0) {  // candidate 0: the raw frames (klb_imageIO.cpp:1690, :1258)
-        return hipMemcpyAsync(d_out, d_in, bytes, hipMemcpyDeviceToDevice, stream) == hipSuccess ? LFM_HIP_OK
-                                                                                                   : LFM_HIP_ERUNTIME;
-    }
     lfm::FrameSet p{d_in, d_prev, d_out, W, H, T, nframes, z0, video_bit & 1, 0};
-    if ((video_bit & 1) && ((z0 & 1) != 0) && d_prev == nullptr) return LFM_HIP_EINVAL;
-    const int force_generic = lfm_hip_force_generic();
-    hipError_t e = hipErrorInvalidValue;
-    switch (family) {
-    case 0: e = lfm::launch_fam<0>(predictor, p, stream, force_generic); break;
-    case 1: e = lfm::launch_fam<1>(predictor, p, stream, force_generic); break;
-    case 2: e = lfm::launch_fam<2>(predictor, p, stream, force_generic); break;
-    }
+    const bool prev_used = (video_bit & 1) && ((z0 & 1) != 0);
+    if (predictor != 0 && prev_used && d_prev == nullptr) return LFM_HIP_EINVAL;
+    const bool aligned = aligned16(d_in) && aligned16(d_out) && (!prev_used || aligned16(d_prev));
+    lfm::LaunchList ll;
+    hipError_t e = lfm::plan_call(p, family, predictor, false, aligned, ll);
+    if (e == hipSuccess) e = lfm::run_launches(ll, p, stream);
     return e == hipSuccess ? LFM_HIP_OK : LFM_HIP_ERUNTIME;
 }
 
@@ -1407,20 +1569,28 @@ extern "C" int lfm_hip_predict_candidates(const uint16_t* d_frame, uint16_t* d_o
     if (!d_frame || !d_out7 || W <= 0 || H <= 0 || T <= 0 || family < 0 || family > 2) return LFM_HIP_EINVAL;
     hipStream_t stream = (hipStream_t)stream_;
     lfm::FrameSet p{d_frame, nullptr, d_out7, W, H, T, 1, 0, 0, 0};
-    if (!lfm::fast_ok(p, lfm_hip_force_generic())) {
-        for (int k = 1; k <= 7; ++k) {
-            const int rc = lfm_hip_predict(d_frame, nullptr, d_out7 + (size_t)(k - 1) * W * H, W, H, 1, T, family, k,
-                                           0, 0, stream_);
-            if (rc != LFM_HIP_OK) return rc;
-        }
-        return LFM_HIP_OK;
-    }
-    hipError_t e = hipErrorInvalidValue;
-    switch (family) {
-    case 0: e = lfm::launch_cands<0>(p, stream); break;
-    case 1: e = lfm::launch_cands<1>(p, stream); break;
-    case 2: e = lfm::launch_cands<2>(p, stream); break;
-    }
+    lfm::LaunchList ll;
+    hipError_t e = lfm::plan_call(p, family, 0, true, aligned16(d_frame) && aligned16(d_out7), ll);
+    if (e == hipSuccess) e = lfm::run_launches(ll, p, stream);
     return e == hipSuccess ? LFM_HIP_OK : LFM_HIP_ERUNTIME;
+}
+
+extern "C" int lfm_hip_predict_plan(int W, int H, int nframes, int T, int family, int predictor, int video_bit, int z0,
+                                    int candidates, int aligned, lfm_predict_launch* out, int cap)
+{
+    if (W <= 0 || H <= 0 || nframes <= 0 || T <= 0 || predictor < 0 || predictor > 7 || family < 0 || family > 2 ||
+        !out || cap <= 0)
+        return -1;
+    lfm::FrameSet p{nullptr, nullptr, nullptr, W, H, T, nframes, z0, video_bit & 1, 0};
+    if (candidates) p = lfm::FrameSet{nullptr, nullptr, nullptr, W, H, T, 1, 0, 0, 0};
+    lfm::LaunchList ll;
+    if (lfm::plan_call(p, family, predictor, candidates != 0, aligned != 0, ll) != hipSuccess || ll.n > cap) return -1;
+    for (int i = 0; i < ll.n; ++i) out[i] = ll.l[i].d;
+    return ll.n;
+}
+
+extern "C" int lfm_hip_predict_set_pieces(int n)
+{
+    return lfm::g_force_pieces.exchange(n > 0 ? n : 0);
 }
 #endif

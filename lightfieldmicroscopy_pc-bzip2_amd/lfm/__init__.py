@@ -48,7 +48,7 @@ EXPORTS = [
     "lfm_writer_flush", "lfm_recover", "lfm_reader_open_live", "lfm_reader_refresh",
     # lfm_hip.h
     "lfm_hip_predict", "lfm_hip_unpredict", "lfm_hip_unpredict_async", "lfm_hip_unpredict_check",
-    "lfm_hip_unpredict_path",
+    "lfm_hip_unpredict_path", "lfm_hip_predict_plan", "lfm_hip_predict_set_pieces",
     "lfm_hip_predict_candidates", "lfm_hip_entropy2d", "lfm_hip_entropy2d_hist", "lfm_hip_select_workspace_bytes",
     "lfm_hip_select",
     "lfm_hip_synth", "lfm_hip_device_count", "lfm_hip_force_generic", "lfm_hip_bzip2_workspace_bytes", "lfm_hip_bzip2_out_cap",
@@ -77,6 +77,13 @@ class EncodeStats(ctypes.Structure):
         d["entropy"] = list(self.entropy)
         d["bz_stage_ms"] = dict(zip(self.BZ_STAGES, list(self.bz_stage_ms)))
         return d
+
+
+class PredictLaunch(ctypes.Structure):
+    """lfm_predict_launch (lfm_hip.h)."""
+    _fields_ = [(f, ctypes.c_int) for f in (
+        "kernel", "first", "nframes", "pairs", "strip", "nstrip", "rows_per_step", "rows_per_piece", "npiece", "R",
+        "RP", "halo", "xcd_map", "grid_x", "grid_y", "threads", "lds_bytes")]
 
 
 class DecodeStats(ctypes.Structure):
@@ -265,6 +272,9 @@ def lib():
         L.lfm_hip_crop_region.argtypes = [vp, u32p, u32p, u32p, ctypes.c_uint32, vp, vp]
     if hasattr(L, "lfm_hip_unpredict_path"):
         L.lfm_hip_unpredict_path.argtypes = [ctypes.c_int] * 3
+    if hasattr(L, "lfm_hip_predict_plan"):
+        L.lfm_hip_predict_plan.argtypes = [ctypes.c_int] * 10 + [ctypes.POINTER(PredictLaunch), ctypes.c_int]
+        L.lfm_hip_predict_set_pieces.argtypes = [ctypes.c_int]
     # the multi-GPU reader, likewise
     intp = ctypes.POINTER(ctypes.c_int)
     if hasattr(L, "lfm_set_decode_devices"):
@@ -1242,6 +1252,36 @@ def unpredict_path(W, H, T):
     """Which inverse-predictor kernel decodes W x H frames of lenslet size T: an
     index into UNPREDICT_PATHS, or -1 for a shape the inverse rejects.  No GPU."""
     return int(lib().lfm_hip_unpredict_path(W, H, T))
+
+
+PREDICT_KERNELS = ("copy", "generic", "ring", "vec", "vec_pair", "cands")
+PREDICT_MAX_LAUNCHES = 7
+
+
+def predict_plan(W, H, nframes, T, family, predictor, video=0, z0=0, candidates=False, aligned=True):
+    """lfm_hip_predict_plan: the launches predict_device (or, with `candidates`,
+    predict_candidates_device) makes for these arguments, in order, as dicts of
+    the lfm_predict_launch fields with the kernel's name from PREDICT_KERNELS.
+    `aligned`: the call's pointers are 16-byte aligned.  Launches nothing; no
+    GPU is needed once predict_set_pieces has forced a piece count."""
+    out = (PredictLaunch * PREDICT_MAX_LAUNCHES)()
+    n = lib().lfm_hip_predict_plan(W, H, nframes, T, FAMILIES.get(family, family), predictor, int(video), z0,
+                                   int(bool(candidates)), int(bool(aligned)), out, PREDICT_MAX_LAUNCHES)
+    if n < 0:
+        raise LfmError("lfm_hip_predict_plan refused %r" % ((W, H, nframes, T, family, predictor, video, z0),))
+    plans = []
+    for i in range(n):
+        d = {f: getattr(out[i], f) for f, _ in PredictLaunch._fields_}
+        d["kernel"] = PREDICT_KERNELS[d["kernel"]]
+        plans.append(d)
+    return plans
+
+
+def predict_set_pieces(n):
+    """lfm_hip_predict_set_pieces, a test hook: force the forward predictor's
+    row-piece count for the whole process (0 = automatic); returns the
+    previous value."""
+    return int(lib().lfm_hip_predict_set_pieces(int(n)))
 
 
 def predict_candidates_device(d_frame, d_out7, W, H, T, family, stream=None):
