@@ -69,6 +69,7 @@
 #include "lfm_bz_caps.h"  // rle_cap, out_cap, sel_cap, kGSize, align_up, max_parts
 #include "lfm_hip.h"
 #include "lfm_huff_heap.h"  // the heap steps of huff_lengths_heap
+#include "lfm_sel_mtf.h"    // the selector move-to-front of huff_final
 
 #ifndef LFM_BWT_FORCE_FULL
 #define LFM_BWT_FORCE_FULL 0  // timing variants: every rotation sorted, no induction
@@ -3127,10 +3128,10 @@ constexpr int kHuffThreads = 256;
 
 // sendMTFValues split across launches so the sequential part (the heap of
 // BZ2_hbMakeCodeLengths) runs SIMT, one table per lane:
-//   huff_init     nGroups and the initial partition (len 0 / 15)
 //   huff_select   x4: selector per 50 symbols (first minimum cost, all tables
 //                 summed at once in 10-bit fields), then symbol frequencies
-//                 per selected table
+//                 per selected table; the first one starts with nGroups and
+//                 the initial partition (lengths 0 / 15)
 //   huff_lengths  x4: BZ2_hbMakeCodeLengths (huffman.c, restated: nodes and
 //                 heap from 1, entry 0 the sentinel, weights carry the depth
 //                 in the low byte), one lane per (stream, table)
@@ -3142,21 +3143,16 @@ __device__ __forceinline__ uint32_t stream_nin(const Batch& B, uint32_t s)
     return nin;
 }
 
-// compress.c's initial partition: the frequencies go to LDS (the greedy walk
-// is sequential and would otherwise wait on a global load per symbol), one
-// lane walks them, all lanes write the lengths
-__global__ __launch_bounds__(64) void huff_init(Batch B)
+// compress.c's initial partition, the prologue of the first huff_select_reg
+// launch: the frequencies go to LDS (the greedy walk is sequential and would
+// otherwise wait on a global load per symbol), one lane walks them; table q
+// then prices symbols pgs[q] .. pge[q] at 0 and the others at 15.  Writes
+// nGroups and nSel for the later launches.
+__device__ __forceinline__ void huff_partition(const Batch& B, uint32_t s, uint32_t t, uint32_t nthreads, uint32_t nMTF,
+                                               int alphaSize, int nGroups, int* mf, int* pgs, int* pge)
 {
-    __shared__ int mf[kMaxAlpha];
-    __shared__ int pgs[kMaxGroups], pge[kMaxGroups];
-    const uint32_t s = blockIdx.x, t = threadIdx.x;
-    if (B.flags[s] & kFlagHost) return;
-    const uint32_t nMTF = B.nmtf[s];
-    const int alphaSize = (int)stream_nin(B, s) + 2;
     const uint32_t* mfreq = B.mtf_freq + (size_t)s * kMaxAlpha;
-    uint8_t* len = B.len + (size_t)s * kMaxGroups * kMaxAlpha;
-    const int nGroups = nMTF < 200 ? 2 : nMTF < 600 ? 3 : nMTF < 1200 ? 4 : nMTF < 2400 ? 5 : 6;
-    for (int v = t; v < kMaxAlpha; v += 64) mf[v] = v < alphaSize ? (int)mfreq[v] : 0;
+    for (int v = t; v < kMaxAlpha; v += nthreads) mf[v] = v < alphaSize ? (int)mfreq[v] : 0;
     __syncthreads();
     if (t == 0) {
         int nPart = nGroups, remF = (int)nMTF, gs = 0;
@@ -3181,10 +3177,6 @@ __global__ __launch_bounds__(64) void huff_init(Batch B)
         B.nsel[s] = (nMTF + kGSize - 1) / kGSize;
     }
     __syncthreads();
-    for (int i = t; i < kMaxGroups * kMaxAlpha; i += 64) {
-        const int q = i / kMaxAlpha, v = i - q * kMaxAlpha;
-        len[i] = (q < nGroups && v < alphaSize && v >= pgs[q] && v <= pge[q]) ? 0 : 15;
-    }
 }
 
 // huff_select with a group's 50 symbols loaded straight into registers (25
@@ -3193,26 +3185,40 @@ __global__ __launch_bounds__(64) void huff_init(Batch B)
 // workgroups per CU to hide the loads.  The last, partial group pads with
 // symbol kMaxAlpha, whose packed lengths are 0 and which is not counted.
 // (A 25 KiB LDS tile of the symbols measured 3.4x slower: fewer workgroups per CU.)
+// FIRST: the first of the kIters launches prices the symbols by the initial
+// partition (huff_partition, walked here: no launch of its own and no 0 / 15
+// length table in memory, which nothing else reads); the later ones by the
+// code lengths huff_lengths_heap left.
+template <bool FIRST>
 __global__ __launch_bounds__(kHuffThreads) void huff_select_reg(Batch B)
 {
     __shared__ uint32_t rfreq[kMaxGroups][kMaxAlpha];
     __shared__ uint64_t lpack[kMaxAlpha + 1];
     __shared__ uint32_t junk[kHuffThreads];
+    __shared__ int pgs[kMaxGroups], pge[kMaxGroups];
     const uint32_t s = blockIdx.x, t = threadIdx.x;
     if (B.flags[s] & kFlagHost) return;
-    const uint32_t nMTF = B.nmtf[s], nSel = B.nsel[s];
-    const int nGroups = (int)B.ngroups[s];
+    const uint32_t nMTF = B.nmtf[s];
+    const uint32_t nSel = FIRST ? (nMTF + kGSize - 1) / kGSize : B.nsel[s];
+    int nGroups;
+    if constexpr (FIRST) nGroups = nMTF < 200 ? 2 : nMTF < 600 ? 3 : nMTF < 1200 ? 4 : nMTF < 2400 ? 5 : 6;
+    else nGroups = (int)B.ngroups[s];
     const int alphaSize = (int)stream_nin(B, s) + 2;
     const uint8_t* len = B.len + (size_t)s * kMaxGroups * kMaxAlpha;
     const uint16_t* mtfv = B.mtfv + (size_t)s * (B.cap + 8);
     uint8_t* sel = B.sel + (size_t)s * B.sel_cap;
-    for (int i = t; i < kMaxGroups * kMaxAlpha; i += kHuffThreads) rfreq[i / kMaxAlpha][i % kMaxAlpha] = 0;
+    // (the walk's frequencies lie in rfreq's first row until it is cleared)
+    if constexpr (FIRST) huff_partition(B, s, t, kHuffThreads, nMTF, alphaSize, nGroups, (int*)&rfreq[0][0], pgs, pge);
     for (int v = t; v <= kMaxAlpha; v += kHuffThreads) {
         uint64_t lp = 0;
         if (v < alphaSize)
-            for (int q = 0; q < nGroups; ++q) lp |= (uint64_t)len[q * kMaxAlpha + v] << (10 * q);
+            for (int q = 0; q < nGroups; ++q) {
+                const uint32_t l = FIRST ? (v >= pgs[q] && v <= pge[q] ? 0u : 15u) : (uint32_t)len[q * kMaxAlpha + v];
+                lp |= (uint64_t)l << (10 * q);
+            }
         lpack[v] = lp;
     }
+    for (int i = t; i < kMaxGroups * kMaxAlpha; i += kHuffThreads) rfreq[i / kMaxAlpha][i % kMaxAlpha] = 0;
     __syncthreads();
     uint64_t lp_hot[4];
 #pragma unroll
@@ -3294,6 +3300,50 @@ __global__ __launch_bounds__(kHuffThreads) void huff_select_reg(Batch B)
 //   * Parents go to global memory (the stream's code table, unused until
 //     huff_final) and come back for the depth pass, whose depths overlay the
 //     lane's own entries.
+
+// Diagnostic build (-DLFM_HUFF_STAMPS, off by default: nothing of it is in the
+// library otherwise): the wave's clock (s_memtime) is read between the phases
+// of heap_code_lengths and around the two halves of huff_final, the time each
+// phase took is summed over a lane's rounds and its largest value over the
+// workgroup's lanes (and over the launches since the last read) is left in
+// g_huff_stamps, which lfm_hip_huff_stamps copies out and clears
+// (scripts/huff_stamps_probe.py).
+// A phase's value is thus a maximum taken apart from the other phases', not one
+// launch's chain: shares of their sum are approximate.
+//   row 0, huff_lengths_heap (all launches since the last read): 0 sentinel fill and frequency
+//          loads, 1 inserts, 2 heap_pref_build, 3 merge trips, 4 depth pass,
+//          5 length stores
+//   row 1, huff_final: 0 the selector wave, 1 the wave of table 0
+#ifdef LFM_HUFF_STAMPS
+constexpr uint32_t kStampWgs = 4096, kStampSlots = 8;
+__device__ unsigned long long g_huff_stamps[2][kStampWgs][kStampSlots];
+struct HuffStamps {
+    unsigned long long last, d[kStampSlots];
+    __device__ __forceinline__ void start()
+    {
+        for (uint32_t p = 0; p < kStampSlots; ++p) d[p] = 0;
+        __builtin_amdgcn_sched_barrier(0);
+        last = __builtin_amdgcn_s_memtime();
+    }
+    __device__ __forceinline__ void mark(uint32_t p)
+    {
+        __builtin_amdgcn_sched_barrier(0);
+        const unsigned long long now = __builtin_amdgcn_s_memtime();
+        __builtin_amdgcn_sched_barrier(0);
+        d[p] += now - last;
+        last = now;
+    }
+    __device__ __forceinline__ void store(uint32_t row, uint32_t p0, uint32_t np) const
+    {
+        if (blockIdx.x < kStampWgs)
+            for (uint32_t p = p0; p < p0 + np; ++p) atomicMax(&g_huff_stamps[row][blockIdx.x][p], d[p]);
+    }
+};
+#define HUFF_STAMPS(x) x
+#else
+#define HUFF_STAMPS(x)
+#endif
+
 template <typename Ent, int kL>
 struct LdsHeap {
     static constexpr uint32_t RS = sizeof(Ent) * kL;  // bytes per entry row
@@ -3345,28 +3395,10 @@ __device__ __forceinline__ void heap_code_lengths(const Batch& B, char* hb, uint
         // heights stop at 30), so the sift needs no bounds: a pop writes kSent
         // where the last entry was, a push overwrites the first one
         constexpr Ent kSent = ~(Ent)0;
-        // upheap for the initial inserts (z = i is the same in every lane
-        // still inserting): the positions z >> j on the way to the root are
-        // read at once, then every one is rewritten without a branch -- the
-        // parent's entry where the key climbs past it (lt), the key where it
-        // stops, the old entry above (the ancestors' weights only grow
-        // downwards, so lt holds for a prefix of the levels; position 0, the
-        // sentinel 0, ends it)
-        auto upheap_init = [&](uint32_t z) {
-            constexpr int D = 9;  // z < 512: z >> 9 is position 0
-            Ent v[D + 1];
-#pragma unroll
-            for (int j = 0; j <= D; ++j) v[j] = ent(z >> j);  // v[0]: the key, the leaf at z
-            __builtin_amdgcn_sched_barrier(0);  // every read goes out before the first wait
-            const Ent k = v[0], kk = k | (Ent)1023;
-            bool below = true;  // the key climbed past the level below
-#pragma unroll
-            for (int j = 0; j < D; ++j) {
-                const bool lt = kk < v[j + 1];
-                ent(z >> j) = lt ? v[j + 1] : (below || j == 0 ? k : v[j]);
-                below = lt;
-            }
-        };
+        // 8-byte global loads per round trip.  32 (five round trips for the
+        // frequencies and the parents instead of nine) measured slower,
+        // 409.3 against 406.8 us per launch: DESIGN 4b
+        constexpr int kLoads = 16;
         // Rounds of the wave: a lane builds its heap (again, with halved
         // weights, after a tree that came out too long), then all merge in
         // lockstep; lanes whose heap is done sit the trips out.  Every loop's
@@ -3374,6 +3406,7 @@ __device__ __forceinline__ void heap_code_lengths(const Batch& B, char* hb, uint
         int retries = 0;
         uint32_t nMerged = (uint32_t)A;  // nodes so far
         bool build = true;
+        HUFF_STAMPS(HuffStamps ts; ts.start();)
         for (int round = 0; round <= kHeapMaxRetries<Ent>; ++round) {
             uint32_t nHeap = 1, tooLong = 0;
             Ent top = 0;
@@ -3384,14 +3417,15 @@ __device__ __forceinline__ void heap_code_lengths(const Batch& B, char* hb, uint
                 // past them
                 ent(0) = 0;
                 for (int e = A + 1; e < kHeapEntries; ++e) ent((uint32_t)e) = kSent;
-                // 32 frequencies per batch of 16 loads (one memory latency per
-                // batch, not per load: the compiler drains vmcnt at loop edges)
-                for (int i0 = 1; i0 <= A; i0 += 32) {
-                    uint2 f[16];
+                // 32 frequencies per batch of kLoads loads (one memory latency
+                // per batch, not per load: the compiler drains vmcnt at loop
+                // edges)
+                for (int i0 = 1; i0 <= A; i0 += 2 * kLoads) {
+                    uint2 f[kLoads];
 #pragma unroll
-                    for (int q = 0; q < 16; ++q) f[q] = ld2(freq, min(i0 - 1 + 2 * q, kMaxAlpha - 2));
+                    for (int q = 0; q < kLoads; ++q) f[q] = ld2(freq, min(i0 - 1 + 2 * q, kMaxAlpha - 2));
 #pragma unroll
-                    for (int q = 0; q < 16; ++q) {
+                    for (int q = 0; q < kLoads; ++q) {
                         const int i = i0 + 2 * q;
                         uint32_t w0 = f[q].x ? f[q].x : 1u, w1 = f[q].y ? f[q].y : 1u;
                         for (int r = 0; r < retries; ++r) {
@@ -3402,8 +3436,14 @@ __device__ __forceinline__ void heap_code_lengths(const Batch& B, char* hb, uint
                         if (i + 1 <= A) ent(i + 1) = ((Ent)w1 << 15) | (Ent)(i + 1);
                     }
                 }
-                for (int i = 1; i <= A; ++i) upheap_init((uint32_t)i);
+                HUFF_STAMPS(ts.mark(0);)
+                // the inserts, level by level (position z is the same in
+                // every lane still inserting): an insert reads its own
+                // ancestors only, seven positions on average, not ten
+                heap_insert_levels<Ent>(acc, (uint32_t)A);
+                HUFF_STAMPS(ts.mark(1);)
                 heap_pref_build<Ent>(acc, m, (uint32_t)A);
+                HUFF_STAMPS(ts.mark(2);)
                 nHeap = (uint32_t)A;
                 nMerged = (uint32_t)A;
                 top = ent(1);
@@ -3417,6 +3457,7 @@ __device__ __forceinline__ void heap_code_lengths(const Batch& B, char* hb, uint
             hmax = min(__builtin_amdgcn_readfirstlane(hmax), (uint32_t)kMaxAlpha);
             for (; hmax > 1u; --hmax)
                 if (build && nHeap > 1u) heap_merge_step_at<Ent>(acc, m, hmax, nHeap, nMerged, top, tooLong);
+            HUFF_STAMPS(ts.mark(3);)
             build = build && tooLong && retries < kHeapMaxRetries<Ent>;
             if (build) ++retries;
             if (!__builtin_amdgcn_ballot_w64(build)) break;
@@ -3425,16 +3466,16 @@ __device__ __forceinline__ void heap_code_lengths(const Batch& B, char* hb, uint
         if (retries) atomicAdd(B.wide_cnt + 1, (uint32_t)retries);  // statistics (LFM_BZ2_STATS)
         // depths top-down (a parent is created after its children)
         dep(nNodes) = 0;
-        // 64 parents per batch of 16 loads, highest nodes first
-        for (int kc = (nNodes - 1) & ~63; kc >= 0; kc -= 64) {
-            uint2 pw[16];
+        // 64 parents per batch of kLoads loads, highest nodes first
+        for (int kc = (nNodes - 1) & ~(4 * kLoads - 1); kc >= 0; kc -= 4 * kLoads) {
+            uint2 pw[kLoads];
 #pragma unroll
-            for (int q = 0; q < 16; ++q) pw[q] = ld2(parent, min(kc / 2 + 2 * q, (2 * kMaxAlpha) / 2 - 2));
+            for (int q = 0; q < kLoads; ++q) pw[q] = ld2(parent, min(kc / 2 + 2 * q, (2 * kMaxAlpha) / 2 - 2));
             // four nodes b .. b + 3 per LDS round trip: their parents' depths
             // are read together, a parent inside the four (the root included)
             // is taken from registers instead
 #pragma unroll
-            for (int q = 15; q >= 0; --q) {
+            for (int q = kLoads - 1; q >= 0; --q) {
                 const int b = kc + 4 * q;
                 const uint32_t p4[4] = {pw[q].x & 0xFFFFu, pw[q].x >> 16, pw[q].y & 0xFFFFu, pw[q].y >> 16};
                 uint32_t d[4], dn[4];
@@ -3451,7 +3492,9 @@ __device__ __forceinline__ void heap_code_lengths(const Batch& B, char* hb, uint
                 }
             }
         }
+        HUFF_STAMPS(ts.mark(4);)
         for (int i = 1; i <= A; ++i) len[i - 1] = (uint8_t)dep(i);
+        HUFF_STAMPS(ts.mark(5); ts.store(0, 0, 6);)
     }
 }
 
@@ -3482,42 +3525,79 @@ __global__ __launch_bounds__(64) void huff_lengths_heap(Batch B, uint32_t nwg_wi
     }
 }
 
-// One wave per stream.  Selector MTF (compress.c, 6 entries): the list is a
-// register of 4-bit entries, a step finds the entry by a zero-nibble test and
-// rotates the nibbles in front of it; 64 selectors are loaded at a time and
-// walked with readlane.  Codes (BZ2_hbAssignCodes) per table in parallel:
-// code = (codes of all shorter lengths, doubled per length) + rank of the
-// symbol among the same-length symbols before it (ballots per length).
-__global__ __launch_bounds__(64) void huff_final(Batch B)
+// Seven waves per stream, each with a chain of its own and nothing shared.
+// Waves 0 .. 5: the codes of table `wave` (BZ2_hbAssignCodes): code = (codes
+// of all shorter lengths, doubled per length) + rank of the symbol among the
+// same-length symbols before it (ballots per length).  Wave 6: the selector
+// MTF (compress.c, 6 entries) as a scan (lfm_sel_mtf.h): a lane holds
+// kSelChunk selectors in registers, sums them up, the wave composes the
+// summaries on top of the carry, the lane replays its chunk from its own list.
+// A pass covers 64 * kSelChunk selectors: a config-3 stream (1 900 .. 2 000)
+// in one, a level-9 block's 18 002 in nine with the list carried.
+constexpr uint32_t kSelChunk = 32;
+constexpr uint32_t kFinalWaves = kMaxGroups + 1;
+static_assert(kSelChunk % 16 == 0, "a lane's chunk is loaded and stored in 16-byte pieces");
+
+__device__ __forceinline__ void sel_mtf_scan(const uint8_t* __restrict__ sel, uint8_t* __restrict__ sm, uint32_t nSel,
+                                             uint32_t lane)
 {
-    const uint32_t s = blockIdx.x, lane = threadIdx.x;
+    constexpr uint32_t NQ = kSelChunk / 16;
+    uint32_t carry = kSelMtfStart;
+    for (uint32_t i0 = 0; i0 < nSel; i0 += kSelMtfLanes * kSelChunk) {
+        const uint32_t b = i0 + lane * kSelChunk;
+        const uint32_t n = selmtf_chunk_count(nSel, i0, lane, kSelChunk);
+        // the selector arrays start 256-byte aligned in the workspace and a
+        // stream's selectors at s * sel_cap, a multiple of 64 (layout()), and
+        // nSel <= sel_cap: a 16-byte piece that starts below nSel is aligned
+        // and lies inside the stream's sel_cap bytes
+        uint32_t w[4 * NQ];
+#pragma unroll
+        for (uint32_t q = 0; q < NQ; ++q) {
+            uint4 v = make_uint4(0u, 0u, 0u, 0u);
+            if (b + 16u * q < nSel) v = *(const uint4*)(sel + b + 16u * q);
+            w[4 * q] = v.x, w[4 * q + 1] = v.y, w[4 * q + 2] = v.z, w[4 * q + 3] = v.w;
+        }
+        auto get = [&](uint32_t g) { return (w[g >> 2] >> (8u * (g & 3u))) & 0xFFu; };
+        uint32_t incl = selmtf_summary(get, n, kSelChunk);
+        if (lane == 0) incl = selmtf_compose(carry, incl);
+#pragma unroll
+        for (uint32_t d = 1; d < kSelMtfLanes; d <<= 1) {
+            const uint32_t prev = (uint32_t)__shfl_up((int)incl, d);
+            const uint32_t both = selmtf_compose(prev, incl);
+            incl = lane >= d ? both : incl;
+        }
+        const uint32_t before = (uint32_t)__shfl_up((int)incl, 1);
+        uint32_t o[4 * NQ];
+#pragma unroll
+        for (uint32_t q = 0; q < 4 * NQ; ++q) o[q] = 0;
+        selmtf_replay(lane ? before : carry, get, [&](uint32_t g, uint32_t j) { o[g >> 2] |= j << (8u * (g & 3u)); }, n,
+                      kSelChunk);
+        // (the bytes of a last piece past nSel: zeros inside sel_cap, never read)
+#pragma unroll
+        for (uint32_t q = 0; q < NQ; ++q)
+            if (b + 16u * q < nSel) *(uint4*)(sm + b + 16u * q) = make_uint4(o[4 * q], o[4 * q + 1], o[4 * q + 2], o[4 * q + 3]);
+        carry = (uint32_t)__builtin_amdgcn_readlane((int)incl, kSelMtfLanes - 1);
+    }
+}
+
+__global__ __launch_bounds__(64 * kFinalWaves) void huff_final(Batch B)
+{
+    const uint32_t s = blockIdx.x, lane = threadIdx.x & 63u;
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     if (B.flags[s] & kFlagHost) return;
     const uint32_t nGroups = B.ngroups[s];
-    const uint32_t nSel = B.nsel[s];
+    HUFF_STAMPS(HuffStamps ts; ts.start();)
+    if (wave == (uint32_t)kMaxGroups) {
+        sel_mtf_scan(B.sel + (size_t)s * B.sel_cap, B.sel_mtf + (size_t)s * B.sel_cap, B.nsel[s], lane);
+        HUFF_STAMPS(ts.mark(0); ts.store(1, 0, 1);)
+        return;
+    }
+    if (wave >= nGroups) return;
     const uint32_t alphaSize = stream_nin(B, s) + 2;
     const uint8_t* len = B.len + (size_t)s * kMaxGroups * kMaxAlpha;
-    {
-        const uint8_t* sel = B.sel + (size_t)s * B.sel_cap;
-        uint8_t* sm = B.sel_mtf + (size_t)s * B.sel_cap;
-        uint32_t pos = 0x543210u;  // entry i in nibble i
-        for (uint32_t i0 = 0; i0 < nSel; i0 += 64) {
-            const uint32_t cnt = min(64u, nSel - i0);
-            const uint32_t v = lane < cnt ? sel[i0 + lane] : 0u;
-            uint32_t out = 0;
-            for (uint32_t g = 0; g < cnt; ++g) {
-                const uint32_t ll = __builtin_amdgcn_readlane(v, g);
-                const uint32_t x = pos ^ (ll * 0x111111u);
-                const uint32_t z = (x - 0x111111u) & ~x & 0x888888u;  // lowest set: the first zero nibble
-                const uint32_t j = (uint32_t)__builtin_ctz(z) >> 2;
-                const uint32_t m = (1u << (4 * (j + 1))) - 1u;
-                pos = (pos & ~m) | (((pos << 4) | ll) & m);
-                out = lane == g ? j : out;
-            }
-            if (lane < cnt) sm[i0 + lane] = (uint8_t)out;
-        }
-    }
     const uint64_t lt = (1ull << lane) - 1ull;
-    for (uint32_t q = 0; q < nGroups; ++q) {
+    {
+        const uint32_t q = wave;
         const uint8_t* lq = len + q * kMaxAlpha;
         uint32_t* code = B.code + ((size_t)s * kMaxGroups + q) * kMaxAlpha;
         uint32_t L[5], c[5];
@@ -3545,6 +3625,7 @@ __global__ __launch_bounds__(64) void huff_final(Batch B)
             if (i < alphaSize) code[i] = c[k];
         }
     }
+    HUFF_STAMPS(ts.mark(1); if (wave == 0) ts.store(1, 1, 1);)
 }
 
 // ------------------------------------------------------------------ emit --
@@ -4621,6 +4702,8 @@ int bzip2_blocks(const void* d_img, const uint32_t dims[5], const uint32_t bs[5]
     if (ws_bytes < layout((uint8_t*)d_ws, streams, raw_cap, multi ? level : 0u, B, S)) return LFM_HIP_EINVAL;
     count = B.nstreams;
     if ((size_t)count * B.cap >= (1ull << 32)) return LFM_HIP_EINVAL;
+    // huff_final moves a stream's selectors in 16-byte pieces
+    if (B.sel_cap % 16 || ((uintptr_t)d_ws & 15)) return LFM_HIP_EINVAL;
     const bool parts = B.parts > 1;
 
     hipError_t e = hipSuccess;
@@ -4682,7 +4765,6 @@ int bzip2_blocks(const void* d_img, const uint32_t dims[5], const uint32_t bs[5]
         return LFM_HIP_ERUNTIME;
     mark(3);
     if (t_hook) t_hook(t_hook_ctx, 2);  // after the wide-stream count's synchronisation: rle2 has run
-    hipLaunchKernelGGL(huff_init, dim3(count), dim3(64), 0, st, B);
     // stage hook 3 once the Huffman tables are done (emission and compaction
     // still queued): a caller may start its next work beside this tail
     // (earlier, after the second or third code-length round, measured slower:
@@ -4705,7 +4787,8 @@ int bzip2_blocks(const void* d_img, const uint32_t dims[5], const uint32_t bs[5]
     }
     hipEvent_t ev_tables = tables_ev.ev;
     for (int it = 0; it < kIters; ++it) {
-        hipLaunchKernelGGL(huff_select_reg, dim3(count), dim3(kHuffThreads), 0, st, B);
+        if (it == 0) hipLaunchKernelGGL(huff_select_reg<true>, dim3(count), dim3(kHuffThreads), 0, st, B);
+        else hipLaunchKernelGGL(huff_select_reg<false>, dim3(count), dim3(kHuffThreads), 0, st, B);
         // uniform heaps, 32 per workgroup: u32 entries for the narrow tables,
         // u64 for the streams rle2 listed, in one launch
         constexpr uint32_t kPlane = 32;  // (stream, table) heaps per wave
@@ -4713,7 +4796,7 @@ int bzip2_blocks(const void* d_img, const uint32_t dims[5], const uint32_t bs[5]
         const uint32_t nw = (nwide * kMaxGroups + kPlane / 2 - 1) / (kPlane / 2);
         hipLaunchKernelGGL(huff_lengths_heap<kPlane>, dim3(nn + nw), dim3(64), 0, st, B, nw, nwide);
     }
-    hipLaunchKernelGGL(huff_final, dim3(count), dim3(64), 0, st, B);
+    hipLaunchKernelGGL(huff_final, dim3(count), dim3(64 * kFinalWaves), 0, st, B);
     mark(4);
     const bool hook3 = t_hook && ev_tables && hipEventRecord(ev_tables, st) == hipSuccess;
     Batch J = B;  // what compaction reads: the slots' streams, or the joined ones
@@ -4801,3 +4884,16 @@ extern "C" int lfm_hip_bzip2_last_stage_ms(float ms[5])
     for (int i = 0; i < 5; ++i) ms[i] = t_stage.last_ms[i];
     return 0;
 }
+
+#ifdef LFM_HUFF_STAMPS
+// the stamps since the last call, 2 x 4096 x 8 values (HuffStamps), then cleared
+extern "C" int lfm_hip_huff_stamps(unsigned long long* out)
+{
+    if (!out || hipDeviceSynchronize() != hipSuccess) return 3;
+    const size_t bytes = sizeof(unsigned long long) * 2 * kStampWgs * kStampSlots;
+    void* d = nullptr;
+    if (hipGetSymbolAddress(&d, HIP_SYMBOL(g_huff_stamps)) != hipSuccess) return 3;
+    if (hipMemcpy(out, d, bytes, hipMemcpyDeviceToHost) != hipSuccess || hipMemset(d, 0, bytes) != hipSuccess) return 3;
+    return 0;
+}
+#endif

@@ -106,6 +106,53 @@ LFM_HD inline void heap_pref_set_any(HeapPref& m, uint32_t p, uint32_t bit)
     for (uint32_t i = 0; i < (uint32_t)kPrefWords; ++i) m.w[i] = wi == i ? heap_put_bit(m.w[i], b, bit) : m.w[i];
 }
 
+// The initial inserts.  Positions 1 .. A hold the leaves in insertion order
+// (an insert's climb only touches positions above it in the tree, all below
+// it in the array) and are inserted in that order, level by level: position z
+// of level J (2^J <= z < 2^(J + 1)) has J ancestors, z >> 1 .. z >> J = 1,
+// read with it in one round trip and rewritten without a branch -- the
+// parent's entry where the key climbs past it, the key where it stops, the
+// old entry above (weights only grow downwards, so the key passes a prefix of
+// the levels; the root ends the climb, position 0 is not read).
+template <int J, typename Ent, typename Acc>
+LFM_HD inline void heap_insert_at(Acc& acc, uint32_t z)
+{
+    Ent v[J + 1];
+#pragma unroll
+    for (int j = 0; j <= J; ++j) v[j] = acc.ld(z >> j);  // v[0]: the key, the leaf at z
+    acc.fence();
+    const Ent k = v[0], kk = k | (Ent)1023;
+    bool below = true;  // the key climbed past the level below
+#pragma unroll
+    for (int j = 0; j < J; ++j) {
+        const bool lt = kk < v[j + 1];
+        acc.st(z >> j, lt ? v[j + 1] : (below ? k : v[j]));
+        below = lt;
+    }
+    acc.st(1u, below ? k : v[J]);
+}
+
+template <int J, typename Ent, typename Acc>
+LFM_HD inline void heap_insert_level(Acc& acc, uint32_t A)
+{
+    const uint32_t last = A < (2u << J) - 1u ? A : (2u << J) - 1u;
+    for (uint32_t z = 1u << J; z <= last; ++z) heap_insert_at<J, Ent>(acc, z);
+}
+
+// all inserts of a heap of A <= 511 leaves (the leaf at position 1 is the heap of one)
+template <typename Ent, typename Acc>
+LFM_HD inline void heap_insert_levels(Acc& acc, uint32_t A)
+{
+    heap_insert_level<1, Ent>(acc, A);
+    heap_insert_level<2, Ent>(acc, A);
+    heap_insert_level<3, Ent>(acc, A);
+    heap_insert_level<4, Ent>(acc, A);
+    heap_insert_level<5, Ent>(acc, A);
+    heap_insert_level<6, Ent>(acc, A);
+    heap_insert_level<7, Ent>(acc, A);
+    heap_insert_level<8, Ent>(acc, A);
+}
+
 // the bits of nodes 1 .. A / 2 from the entries, after the initial inserts
 // (every other node's children are sentinels), eight pairs per round trip
 template <typename Ent, typename Acc>
